@@ -12,9 +12,15 @@ of state resident in HBM:
                                                       k_publish, k_send,
                                                       k_commit, k_handle_control
 W untimed warmup ticks, then exactly K timed ticks bracketed by barrier +
-device sync; max over ranks; rank 0 prints one JSON line.  Per-kernel-class
-device time comes from HIP events recorded on the engine stream around every
-launch inside the timed region (gsim_profile).
+device sync; max over ranks; rank 0 prints one JSON line.
+
+A plain run does only that: set-up, warm-up, the K timed ticks, the outputs of
+the last tick if --dump-outputs DIR is given, and the headline line (value,
+ms_per_step, deliveries).  --full adds everything else to the line: per-kernel-
+class device time from HIP events recorded on the engine stream around every
+launch inside the timed region (gsim_profile), the census and gossip counters,
+the roofline figures, the box's clocks, the device memory in use and the CPU
+baseline (the C oracle timed on a sample of the same workload).
 
 Multi-GPU: the one network is graph-sharded over the ranks
 (contiguous peer ranges, one shard per GPU), with the halo exchange of message
@@ -44,8 +50,11 @@ PROBE_MISS_PER_S = 54.1e9      # 2 GB table: every load an L2 miss
 PROBE_L2_REQ_PER_S = 251.2e9   # 4 MB table: L2-resident
 ROUNDS = 10                    # propagation rounds per heartbeat
 MSG_RATE = 4.0                 # messages / s / topic
-MSG_RING = 1024                # live-message window: >= 16 heartbeats of publications, so no slot
-                               # is republished while its message can still be gossiped or promised
+MSG_RING = 2048                # live-message window: ~32 heartbeats of publications (64 a tick at C3).
+                               # A slot may be republished 12 heartbeats (history + promise window + 2)
+                               # after its message's last new delivery; 1024 slots (~16 heartbeats) left
+                               # no margin for the late IWANT deliveries and the Poisson spread, and a
+                               # long run (--steps in the hundreds) was refused for an early republication
 DUP_BYTES, FIRST_BYTES = 40, 72   # algorithmic bytes per delivery
 
 CONFIGS = {
@@ -464,6 +473,43 @@ def replica_seeds(rank: int):
     return 1 + rank, 2 + rank
 
 
+DUMP_SAMPLE = 1 << 20          # elements kept of an output larger than this
+DUMP_FIELD_MAX = 1 << 30       # a state field above this many bytes is not read back
+
+
+def _dump_sample(a: np.ndarray, seed: int) -> np.ndarray:
+    """The flat array, or (above DUMP_SAMPLE elements) its values at DUMP_SAMPLE
+    seeded positions: the same positions in every run of the same shape."""
+    a = a.reshape(-1)
+    if a.size > DUMP_SAMPLE:
+        a = a[np.sort(np.random.default_rng(seed).integers(0, a.size, DUMP_SAMPLE))]
+    return a
+
+
+def dump_outputs(eng, net, n_topics: int, path: str, write: bool = True, fields: bool = True):
+    """--dump-outputs: what a caller of the engine holds after the last timed
+    tick, one DIR/<name>.npy each (float64, the flags float32): the scores every
+    observer holds of its connections, the delivery and gossip totals, the
+    census of the topic records, and (single engine, while the field fits
+    DUMP_FIELD_MAX) the per-topic mesh / fanout flags and the behaviour
+    penalties.  Arrays above DUMP_SAMPLE elements are sampled at seeded
+    positions, so two builds run with the same arguments compare output for
+    output."""
+    from gsim import _abi
+    out = {"scores": _dump_sample(eng.scores(), 101).astype(np.float64),
+           "msg_stats": np.asarray(eng.msg_stats(), dtype=np.float64),
+           "gossip_stats": np.asarray(list(eng.gossip_stats().values()), dtype=np.float64),
+           "census": np.asarray(list(eng.census().values()), dtype=np.float64)}
+    if fields and n_topics * net.e <= DUMP_FIELD_MAX:
+        out["tflags"] = _dump_sample(eng.read(_abi.F_TFLAGS), 102).astype(np.float32)
+    if fields and 8 * net.e <= DUMP_FIELD_MAX:
+        out["behaviour_penalty"] = _dump_sample(eng.read(_abi.F_BP), 103).astype(np.float64)
+    if write:
+        os.makedirs(path, exist_ok=True)
+        for name, a in out.items():
+            np.save(os.path.join(path, name + ".npy"), a)
+
+
 def load_traffic(workload: str):
     path = os.path.join(REPO, "profiles", "traffic.json")
     if not os.path.exists(path):
@@ -480,7 +526,15 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--config", default="c3", choices=sorted(CONFIGS))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline figure: per-kernel-class device time (HIP events inside the timed "
+                         "region), census and gossip counters, roofline figures, the box's clocks, device memory "
+                         "in use and the CPU baseline (a plain run measures and prints only the headline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step left a caller (scores, delivery and "
+                         "gossip totals, census, mesh flags, behaviour penalties; seeded samples of the large "
+                         "ones) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--cpu-full", action="store_true",
                     help="time only the C oracle on the config's full network (no GPU): one tick per leg after "
                          "GSIM_CPU_WARMUP (1) warm-up ticks; GSIM_CPU_LEGS=all,single "
@@ -549,12 +603,13 @@ def main():
     eng, net = build_engine(cfg, seed=g_seed, device=local, scen=scen, shard=shard)
     E = net.e
     hbm_used = None
-    try:                                         # device memory in use once the state is resident
-        import torch
-        free_b, total_b = torch.cuda.mem_get_info(local)
-        hbm_used = (total_b - free_b) / 1e9
-    except Exception:
-        pass
+    if args.full:
+        try:                                     # device memory in use once the state is resident
+            import torch
+            free_b, total_b = torch.cuda.mem_get_info(local)
+            hbm_used = (total_b - free_b) / 1e9
+        except Exception:
+            pass
     ticks = range(1, args.warmup + args.steps + 1)
     rate = scen.get("msg_rate", MSG_RATE)
     sched = message_schedule(n, T, ticks, seed=s_seed, sub=net.sub if "zipf_per_peer" in scen else None, rate=rate)
@@ -567,9 +622,9 @@ def main():
     run_ticks(eng, kk, args.warmup, sched, churn, px=bool(scen.get("px")))
     kk += args.warmup
     eng.synchronize()
-    census0 = eng.census()
+    census0 = eng.census() if args.full else None
     stats0 = eng.msg_stats()
-    gossip0 = eng.gossip_stats()
+    gossip0 = eng.gossip_stats() if args.full else None
     local_stats0 = eng.local_msg_stats() if sharded else stats0
 
     def barrier():
@@ -580,7 +635,8 @@ def main():
             torch.cuda.synchronize()
 
     barrier()
-    eng.profile(True)
+    if args.full:
+        eng.profile(True)
     eng.synchronize()
     global CALLTIME
     if args.calltime:
@@ -610,16 +666,19 @@ def main():
               file=sys.stderr)
         CALLTIME = None
     per_shard = None
-    if shard is not None and world == 1:          # in-process shards: each one's kernel time
+    if not args.full:
+        prof = None
+    elif shard is not None and world == 1:        # in-process shards: each one's kernel time
         per_shard = eng.profile_read_shards()
         prof = {c: (sum(p[c][0] for p in per_shard), sum(p[c][1] for p in per_shard)) for c in per_shard[0]}
     else:
         prof = eng.profile_read()
-    eng.profile(False)
+    if args.full:
+        eng.profile(False)
     local_stats1 = eng.local_msg_stats() if sharded else None
-    census1 = eng.census()
+    census1 = eng.census() if args.full else None
     stats1 = eng.msg_stats()
-    gossip1 = eng.gossip_stats()
+    gossip1 = eng.gossip_stats() if args.full else None
     if sharded:
         # group totals are already the whole job's: only the wall time is reduced
         wall, _ = job_totals(wall, 0.0, dist, f"cuda:{local}")
@@ -627,13 +686,39 @@ def main():
     else:
         wall, deliveries = job_totals(wall, float(stats1[0] - stats0[0]), dist, f"cuda:{local}")
 
-    if rank == 0:
-        K = args.steps
-        workload = (f"{args.config}: {n} peers{' (reduced: --peers)' if args.peers else ''}, "
-                    f"{describe_graph(cfg, scen)}, {T} topics, beacon-style params, "
-                    f"{rate:g} msg/s/topic, {ROUNDS} rounds/heartbeat")
-        # peer-heartbeats of the whole job: one network (sharded) or one per rank
-        value = n * (1 if sharded else world) * K / wall
+    if args.dump_outputs:
+        # every rank reads (a group's reads are its ranks' together); rank 0 writes its own
+        dump_outputs(eng, net, T, args.dump_outputs, write=rank == 0, fields=shard is None)
+
+    K = args.steps
+    workload = (f"{args.config}: {n} peers{' (reduced: --peers)' if args.peers else ''}, "
+                f"{describe_graph(cfg, scen)}, {T} topics, beacon-style params, "
+                f"{rate:g} msg/s/topic, {ROUNDS} rounds/heartbeat")
+    # peer-heartbeats of the whole job: one network (sharded) or one per rank
+    value = n * (1 if sharded else world) * K / wall
+    if rank == 0 and not args.full:
+        print(json.dumps({
+            "metric": "peer-heartbeat updates/sec + msg-edge deliveries/sec, 1M-peer gossipsub sim",
+            "value": value,
+            "unit": "peer-heartbeat updates/sec",
+            "n_gpus": world,
+            "steps": K,
+            "warmup": args.warmup,
+            "ms_per_step": wall / K * 1e3,
+            "higher_is_better": True,
+            "scaling": "strong" if sharded else "weak",
+            "vs_baseline": None,
+            "dtype": "f64",
+            "data": f"synthetic (seeded {'power-law' if 'power_law' in scen else 'random-regular'} graph, "
+                    "Philox-seeded steady-state counters and meshes, Poisson message publications)",
+            "config": {"workload": workload, "peers_per_gpu": n, "degree": k, "topics": T,
+                       "edge_topic_records": E * T, "rounds_per_heartbeat": ROUNDS},
+            "msg_edge_deliveries_per_sec": deliveries / wall,
+            "deliveries_per_tick": {"accepted": (stats1[0] - stats0[0]) / K, "first": (stats1[1] - stats0[1]) / K,
+                                    "duplicate": (stats1[2] - stats0[2]) / K, "graylisted": (stats1[3] - stats0[3]) / K},
+            "host_syncs_per_tick": (syncs1 - syncs0) / K,
+        }), flush=True)
+    elif rank == 0:
         kms = {c: ms / K for c, (ms, _) in prof.items()}        # per tick
         launches = {c: cnt for c, (_, cnt) in prof.items()}
         # refresh+score: census-based compulsory bytes per launch

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""One-line summary of a bench.py JSON line: tools/bench_summary.py FILE"""
+"""One-line summary of a `bench.py --full` JSON line: tools/bench_summary.py FILE"""
 import json
 import sys
 

@@ -16,7 +16,7 @@ if [ -n "${PYTEST_K:-}" ]; then
 fi
 for v in default ${VARIANTS:-}; do
   if [ "$v" = default ]; then unset GSIM_LIB; else export GSIM_LIB="$ROOT/go-libp2p-pubsub_amd/libgsim_$v.so"; fi
-  timeout -k 10 500 python -u bench.py --config "${CONFIG:-c5}" --steps "${STEPS:-4}" --warmup 2 --no-cpu-baseline \
+  timeout -k 10 500 python -u bench.py --config "${CONFIG:-c5}" --steps "${STEPS:-4}" --warmup 2 --full --no-cpu-baseline \
     > "$OUT/bench_$v.json" 2> "$OUT/bench_$v.err" || { echo "bench $v rc=$?"; tail -5 "$OUT/bench_$v.err"; exit 1; }
   echo "== $v"; python3 tools/bench_summary.py "$OUT/bench_$v.json" | grep -v "^c5:"
 done

@@ -11,7 +11,7 @@ for r in $(seq 1 "${ROUNDS:-2}"); do
   for arm in ${LIBS}; do
     name="${arm%%:*}"; lib="$ROOT/${arm#*:}"
     GSIM_GROUP_SERIAL=1 GSIM_LIB="$lib" timeout -k 10 300 python bench.py --shards "${K:-8}" --steps "${STEPS:-3}" --warmup 2 \
-      --no-cpu-baseline > "$OUT/s_${name}_$r.json" 2> "$OUT/s_${name}_$r.err"
+      --full --no-cpu-baseline > "$OUT/s_${name}_$r.json" 2> "$OUT/s_${name}_$r.err"
     python3 -c "
 import json,sys
 d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

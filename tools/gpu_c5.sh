@@ -15,13 +15,13 @@ if [ -n "${PYTEST_K:-}" ]; then
   grep -E "^E |FAILED|passed|failed" "$OUT/pytest_gpu.log" | head -20
   [ $rc -ne 0 ] && exit $rc
 fi
-timeout -k 10 700 python -u bench.py --config c5 --steps "${STEPS:-4}" --warmup 2 --no-cpu-baseline ${BENCH_ARGS:-} \
+timeout -k 10 700 python -u bench.py --config c5 --steps "${STEPS:-4}" --warmup 2 --full --no-cpu-baseline ${BENCH_ARGS:-} \
   > "$OUT/bench_c5.json" 2> "$OUT/bench_c5.err" || { echo "bench rc=$?"; tail -20 "$OUT/bench_c5.err"; exit 1; }
 python3 tools/bench_summary.py "$OUT/bench_c5.json"
 [ -n "${NO_PROF:-}" ] && exit 0
 export TMPDIR=/tmp
 cd /tmp
 timeout -k 10 700 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof" -o s \
-  -- python3 "$ROOT/bench.py" --config c5 --steps 3 --warmup 1 --no-cpu-baseline ${BENCH_ARGS:-} > "$OUT/prof.json" 2> "$OUT/prof.err" \
+  -- python3 "$ROOT/bench.py" --config c5 --steps 3 --warmup 1 --full --no-cpu-baseline ${BENCH_ARGS:-} > "$OUT/prof.json" 2> "$OUT/prof.err" \
   || { echo "prof rc=$?"; tail -20 "$OUT/prof.err"; exit 1; }
 python3 "$ROOT/tools/trace_summary.py" "$OUT/prof/s_kernel_trace.csv" 1 > "$OUT/prof_summary.txt"; head -26 "$OUT/prof_summary.txt"

@@ -15,21 +15,21 @@ OUT="$ROOT/gpurun_out/$TAG"
 mkdir -p "$OUT"
 cd "$ROOT"
 if [ -z "${NO_BENCH:-}" ]; then
-  timeout -k 10 600 python -u bench.py --steps "$STEPS" --warmup 3 ${BENCH_ARGS:-} > "$OUT/bench.json" 2> "$OUT/bench.err" \
+  timeout -k 10 600 python -u bench.py --steps "$STEPS" --warmup 3 --full ${BENCH_ARGS:-} > "$OUT/bench.json" 2> "$OUT/bench.err" \
     || { echo "bench rc=$?"; tail -20 "$OUT/bench.err"; exit 1; }
   python3 tools/bench_summary.py "$OUT/bench.json"
 fi
 export TMPDIR=/tmp
 cd /tmp
 timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof" -o s \
-  -- python3 "$ROOT/bench.py" --steps "$STEPS" --warmup 3 --no-cpu-baseline ${BENCH_ARGS:-} > "$OUT/prof.json" 2> "$OUT/prof.err" \
+  -- python3 "$ROOT/bench.py" --steps "$STEPS" --warmup 3 --full --no-cpu-baseline ${BENCH_ARGS:-} > "$OUT/prof.json" 2> "$OUT/prof.err" \
   || { echo "prof rc=$?"; tail -20 "$OUT/prof.err"; exit 1; }
 python3 "$ROOT/tools/trace_summary.py" "$OUT/prof/s_kernel_trace.csv" 1 > "$OUT/prof_summary.txt"; head -14 "$OUT/prof_summary.txt"
 KRE="${KRE:-k_refresh_score<true, true>|k_send_tm|k_commit|k_heartbeat<32>}"
 pass() {
   local name="$1"; shift
   timeout -s KILL 150 rocprofv3 --kernel-trace --pmc "$@" --kernel-include-regex "$KRE" -d "$OUT/pmc_$name" -o p \
-    --output-format csv -- python3 "$ROOT/bench.py" --steps 2 --warmup 1 --no-cpu-baseline ${BENCH_ARGS:-} \
+    --output-format csv -- python3 "$ROOT/bench.py" --steps 2 --warmup 1 --full --no-cpu-baseline ${BENCH_ARGS:-} \
     > "$OUT/pmc_$name.log" 2>&1
   local rc=$?
   echo "pmc $name rc=$rc"

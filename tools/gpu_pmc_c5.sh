@@ -13,7 +13,7 @@ cd /tmp
 pass() {
   local name="$1"; shift
   timeout -s KILL 400 rocprofv3 --kernel-trace --pmc "$@" --kernel-include-regex "$KRE" -d "$OUT/pmc_$name" -o p \
-    --output-format csv -- python3 "$ROOT/bench.py" --config c5 --steps 1 --warmup 1 --no-cpu-baseline ${BENCH_ARGS:-} \
+    --output-format csv -- python3 "$ROOT/bench.py" --config c5 --steps 1 --warmup 1 --full --no-cpu-baseline ${BENCH_ARGS:-} \
     > "$OUT/pmc_$name.log" 2>&1
   local rc=$?
   echo "pmc $name rc=$rc"

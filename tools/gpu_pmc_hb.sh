@@ -10,7 +10,7 @@ export TMPDIR=/tmp
 cd /tmp
 timeout -s KILL 240 rocprofv3 --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_INSTS_LDS SQ_BUSY_CYCLES SQ_WAVE_CYCLES \
   --kernel-include-regex "k_heartbeat<32>" -d "$OUT/hb_sq" -o run --output-format csv \
-  -- python3 "$ROOT/bench.py" --steps 3 --warmup 2 --no-cpu-baseline > "$OUT/hb_sq.log" 2>&1 || { echo "rc=$?"; tail -5 "$OUT/hb_sq.log"; exit 1; }
+  -- python3 "$ROOT/bench.py" --steps 3 --warmup 2 --full --no-cpu-baseline > "$OUT/hb_sq.log" 2>&1 || { echo "rc=$?"; tail -5 "$OUT/hb_sq.log"; exit 1; }
 python3 - "$OUT" <<'PY'
 import csv, collections, glob, sys
 out = sys.argv[1]

@@ -14,7 +14,7 @@ cd /tmp
 run() {
   local name="$1" kre="$2"; shift 2
   timeout -s KILL 240 rocprofv3 --pmc "$@" --kernel-include-regex "$kre" -d "$OUT/$name" -o run --output-format csv \
-    -- python3 "$ROOT/bench.py" --steps 2 --warmup 1 --no-cpu-baseline > "$OUT/$name.log" 2>&1
+    -- python3 "$ROOT/bench.py" --steps 2 --warmup 1 --full --no-cpu-baseline > "$OUT/$name.log" 2>&1
   local rc=$?
   echo "$name rc=$rc"
   return $rc

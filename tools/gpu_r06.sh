@@ -16,7 +16,7 @@ if [ -z "${NO_SUITE:-}" ]; then
   tail -1 "$OUT/smoke.log"
 fi
 for c in ${CONFIGS:-c3 c2 c4}; do
-  timeout -k 10 300 python -u bench.py --config "$c" --steps "${STEPS:-10}" --warmup 2 --no-cpu-baseline \
+  timeout -k 10 300 python -u bench.py --config "$c" --steps "${STEPS:-10}" --warmup 2 --full --no-cpu-baseline \
     > "$OUT/bench_$c.json" 2> "$OUT/bench_$c.err" || { echo "bench $c rc=$?"; tail -5 "$OUT/bench_$c.err"; exit 1; }
   python3 -c "import json,sys; d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]); print(sys.argv[2], round(d['ms_per_step'],3), {k: round(v,3) for k,v in d['kernel_ms_per_tick'].items() if v > 0.01})" "$OUT/bench_$c.json" "$c"
 done

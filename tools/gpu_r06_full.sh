@@ -14,7 +14,7 @@ if [ -z "${NO_FULL:-}" ]; then
   [ $rc -ne 0 ] && exit $rc
 fi
 if [ -z "${NO_C5:-}" ]; then
-  timeout -k 10 900 python -u bench.py --config c5 --steps "${C5_STEPS:-10}" --warmup "${C5_WARMUP:-10}" ${C5_ARGS:-} \
+  timeout -k 10 900 python -u bench.py --config c5 --steps "${C5_STEPS:-10}" --warmup "${C5_WARMUP:-10}" --full ${C5_ARGS:-} \
     > "$OUT/bench_c5.json" 2> "$OUT/bench_c5.err" &
   pid=$!
   while kill -0 $pid 2>/dev/null; do sleep 30; echo "c5 running $(date +%T)"; done

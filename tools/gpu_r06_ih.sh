@@ -10,7 +10,7 @@ mkdir -p "$OUT"
 L=go-libp2p-pubsub_amd
 run_c5() {   # lib tag [env]
   env ${3:-} GSIM_LIB="$1" timeout -k 10 600 python -u bench.py --config c5 --steps "${STEPS:-3}" --warmup 10 \
-    --no-cpu-baseline > "$OUT/$2.json" 2> "$OUT/$2.err" &
+    --full --no-cpu-baseline > "$OUT/$2.json" 2> "$OUT/$2.err" &
   local pid=$!
   while kill -0 $pid 2>/dev/null; do sleep 30; echo "$2 running $(date +%T)"; done
   wait $pid || { echo "$2 rc=$?"; tail -5 "$OUT/$2.err"; return 1; }

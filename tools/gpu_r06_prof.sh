@@ -10,12 +10,12 @@ cd /tmp
 export TMPDIR=/tmp
 for CFG in ${CONFIGS:-c2 c4}; do
   timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/$CFG" -o s -- \
-    python3 "$ROOT/bench.py" --config "$CFG" --steps 20 --warmup 2 --no-cpu-baseline > "$OUT/$CFG.json" 2> "$OUT/$CFG.err" || exit $?
+    python3 "$ROOT/bench.py" --config "$CFG" --steps 20 --warmup 2 --full --no-cpu-baseline > "$OUT/$CFG.json" 2> "$OUT/$CFG.err" || exit $?
   TOPK=40 python3 "$ROOT/tools/trace_summary.py" "$OUT/$CFG/s_kernel_trace.csv" 1 | tee "$OUT/${CFG}_summary.txt"
 done
 if [ -n "${C5:-}" ]; then
   timeout -k 10 900 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/c5" -o s -- \
-    python3 "$ROOT/bench.py" --config c5 --steps ${C5_STEPS:-3} --warmup 10 --no-cpu-baseline > "$OUT/c5.json" 2> "$OUT/c5.err" &
+    python3 "$ROOT/bench.py" --config c5 --steps ${C5_STEPS:-3} --warmup 10 --full --no-cpu-baseline > "$OUT/c5.json" 2> "$OUT/c5.err" &
   pid=$!
   while kill -0 $pid 2>/dev/null; do sleep 30; echo "c5 running $(date +%T)"; done
   wait $pid || exit 1

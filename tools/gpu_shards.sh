@@ -19,7 +19,7 @@ fi
 for k in ${KS:-8}; do
   for pull in ${MODES:-0 1}; do
     GSIM_GROUP_SERIAL=1 GSIM_SHARD_PULL=$pull timeout -k 10 400 python bench.py --config "${CONFIG:-c3}" --shards "$k" \
-      --steps "${STEPS:-3}" --warmup 1 --no-cpu-baseline > "$OUT/k${k}_pull${pull}.json" 2> "$OUT/k${k}_pull${pull}.err"
+      --steps "${STEPS:-3}" --warmup 1 --full --no-cpu-baseline > "$OUT/k${k}_pull${pull}.json" 2> "$OUT/k${k}_pull${pull}.err"
     rc=$?
     [ $rc -ne 0 ] && { tail -20 "$OUT/k${k}_pull${pull}.err"; exit $rc; }
     python3 -c "import json,sys; d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]); print(sys.argv[2], round(d['ms_per_step'],2), d['kernel_ms_per_tick_shards'], {k: round(v,2) for k,v in d['kernel_ms_per_tick'].items() if v > 0.05})" "$OUT/k${k}_pull${pull}.json" "K=$k pull=$pull"
