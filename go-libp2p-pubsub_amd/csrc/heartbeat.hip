@@ -19,7 +19,9 @@
 
 using namespace gsim;
 
-constexpr int kGiantRow = 8192;   // longest row the heartbeat takes (k_heartbeat_hub_g)
+constexpr int kGiantRow = 8192;   // longest row of the block classes (k_heartbeat_hub_g); longer rows are "wide"
+constexpr int kWideB = 1024;      // threads of a wide row's block = positions per tile
+constexpr int kWideBytes = 64;    // scratch per row position of a wide row (WideRow, end of file)
 // row positions per thread of the heartbeat's hub classes (below)
 #ifndef GSIM_HB_HUBV
 #define GSIM_HB_HUBV 2
@@ -63,6 +65,13 @@ struct Extra {
     int64_t nh8192 = 0;
     void* d_gscratch = nullptr;
     int64_t gscratch_blocks = 0;
+    // wide rows (more than kGiantRow connections, no upper bound): one block
+    // walks the row in tiles of its own width, every per-position value in a
+    // slice of global scratch sized by the longest wide row (wide_P positions,
+    // kWideBytes each), one slice per block of the launches
+    int64_t nwide = 0;
+    void* d_wscratch = nullptr;
+    int64_t wide_blocks = 0, wide_P = 0;
     // peer exchange (gsim_gossipsub_params.do_px): topics with PX PRUNEs per
     // observer, connection attempts per edge, the GRAFT RPCs that turned PX off
     uint64_t* d_pxo = nullptr;
@@ -1619,22 +1628,17 @@ __device__ __forceinline__ void wave_lds_sync()
 // ROW: the longest row staged (WV waves per block, ROW scores and keys each):
 // <kPxRow, 4> walks the owned observers with rows of at most kPxRow,
 // <4 kPxRow, 1> the hub list `rows` (rows of kPxRow+1 .. 4 kPxRow).
-template <int ROW, int WV, bool SPLIT = false>
-__global__ __launch_bounds__(64 * WV) void k_px_emit(HbArgs a_, int live, uint32_t key_tick, uint32_t purpose,
-                                                     const uint32_t* rows, int64_t nrows)
+// The kernel's body: sc / cb / pb are the observer's scores, the topic's
+// candidate bits and their draws (LDS of ROW positions; the wide class: the
+// block's scratch slice, written and read between the SPLIT barriers), lst the
+// wave's list of smallest keys (LDS).
+template <int ROW, int WV, bool SPLIT>
+__device__ __forceinline__ void px_emit_rows(const HbArgs& a_, int live, uint32_t key_tick, uint32_t purpose,
+                                             const uint32_t* rows, int64_t nrows, double* sc, uint64_t* cb,
+                                             uint32_t* pb, uint64_t* lst)
 {
     const HbArgs& a = a_;
-    // SPLIT (hub rows): the block's waves share one observer (its scores, each
-    // topic's candidates and draws) and take its PRUNEs in turn
-    __shared__ double s_sc[SPLIT ? 1 : WV][ROW];
-    __shared__ uint64_t s_cb[SPLIT ? 1 : WV][ROW / 64];          // the topic's candidates (makePrune's filter)
-    __shared__ uint32_t s_pb[SPLIT ? 1 : WV][ROW];               // ... and their draws (px_base)
-    __shared__ uint64_t s_lst[WV][kPxList];                      // a PRUNE's smallest keys
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    double* sc = s_sc[SPLIT ? 0 : wid];
-    uint64_t* cb = s_cb[SPLIT ? 0 : wid];
-    uint32_t* pb = s_pb[SPLIT ? 0 : wid];
-    uint64_t* lst = s_lst[wid];
     const int64_t nobs = rows ? nrows : a.ohi - a.olo;
     constexpr int OPB = SPLIT ? 1 : WV;                          // observers per block
     const int slot = SPLIT ? 0 : wid;
@@ -1807,12 +1811,28 @@ __global__ __launch_bounds__(64 * WV) void k_px_emit(HbArgs a_, int live, uint32
     }
 }
 
+template <int ROW, int WV, bool SPLIT = false>
+__global__ __launch_bounds__(64 * WV) void k_px_emit(HbArgs a_, int live, uint32_t key_tick, uint32_t purpose,
+                                                     const uint32_t* rows, int64_t nrows)
+{
+    // SPLIT (hub rows): the block's waves share one observer (its scores, each
+    // topic's candidates and draws) and take its PRUNEs in turn
+    __shared__ double s_sc[SPLIT ? 1 : WV][ROW];
+    __shared__ uint64_t s_cb[SPLIT ? 1 : WV][ROW / 64];          // the topic's candidates (makePrune's filter)
+    __shared__ uint32_t s_pb[SPLIT ? 1 : WV][ROW];               // ... and their draws (px_base)
+    __shared__ uint64_t s_lst[WV][kPxList];                      // a PRUNE's smallest keys
+    const int wid = threadIdx.x >> 6;
+    px_emit_rows<ROW, WV, SPLIT>(a_, live, key_tick, purpose, rows, nrows, s_sc[SPLIT ? 0 : wid], s_cb[SPLIT ? 0 : wid],
+                                 s_pb[SPLIT ? 0 : wid], s_lst[wid]);
+}
+
 // makePrune's PX lists of every observer that sent PX PRUNEs: rows of at most
 // 256 connections a wave each (4 observers per block), hub rows (257-1024,
 // 1025-4096) a block of 4 waves each sharing the observer's scores and taking
 // its PRUNEs in turn (a hub's GRAFT replies are many: one wave made c5's hub
 // pass 20 ms per tick).
 constexpr int kPxSmall = 256;
+static void launch_px_emit_wide(gsim_handle* h, const HbArgs& a, int live, uint32_t key_tick, uint32_t purpose);
 static void launch_px_emit(gsim_handle* h, const HbArgs& a, int live, uint32_t key_tick, uint32_t purpose)
 {
     const Extra* x = h->x;
@@ -1830,6 +1850,7 @@ static void launch_px_emit(gsim_handle* h, const HbArgs& a, int live, uint32_t k
     if (x->nh8192)   // (scores, candidate bits and draws of 8192 positions: 97 KB of LDS)
         hipLaunchKernelGGL((k_px_emit<kGiantRow, 4, true>), dim3((uint32_t)std::min<int64_t>(x->nh8192, 65536)),
                            dim3(256), 0, h->stream, a, live, key_tick, purpose, rh + x->nh1024 + x->nh4096, x->nh8192);
+    if (x->nwide) launch_px_emit_wide(h, a, live, key_tick, purpose);
 }
 
 // Connection attempts to connections (the connector, gossipsub.go:941-973):
@@ -1942,7 +1963,7 @@ void row_classes(gsim_handle* h, RowClasses* rc)
 {
     const Extra* x = h->x;
     if (!x) { *rc = RowClasses{nullptr, 0, 0, h->ohi() - h->olo(), 0}; return; }
-    *rc = RowClasses{x->d_rows, x->n16, x->n32, x->n64, x->nh256 + x->nh1024 + x->nh4096 + x->nh8192};
+    *rc = RowClasses{x->d_rows, x->n16, x->n32, x->n64, x->nh256 + x->nh1024 + x->nh4096 + x->nh8192 + x->nwide};
 }
 
 int px_import(gsim_handle* h, const uint64_t* d_in, int64_t n)
@@ -2513,11 +2534,11 @@ int alloc_extra(gsim_handle* h)
     e = stream_copy(h, rp.data(), h->d_row_ptr, sizeof(uint32_t) * rp.size(), hipMemcpyDeviceToHost);
     if (e != hipSuccess) return hip_check(h, e, "row_ptr readback");
     uint32_t md = 0, mdall = 0;
-    std::vector<uint32_t> cls[7];
+    std::vector<uint32_t> cls[8];
     for (int64_t i = h->olo(); i < h->ohi(); ++i) {
         const uint32_t d = rp[(size_t)i + 1] - rp[(size_t)i];
         md = std::max(md, d);
-        cls[d <= 16 ? 0 : d <= 32 ? 1 : d <= 64 ? 2 : d <= 256 ? 3 : d <= 1024 ? 4 : d <= 4096 ? 5 : 6].push_back((uint32_t)i);
+        cls[d <= 16 ? 0 : d <= 32 ? 1 : d <= 64 ? 2 : d <= 256 ? 3 : d <= 1024 ? 4 : d <= 4096 ? 5 : d <= (uint32_t)kGiantRow ? 6 : 7].push_back((uint32_t)i);
     }
     for (int64_t i = 0; i < h->n; ++i) mdall = std::max(mdall, rp[(size_t)i + 1] - rp[(size_t)i]);
     if (!h->all_joined) {
@@ -2555,13 +2576,23 @@ int alloc_extra(gsim_handle* h)
     h->x->n16 = (int64_t)cls[0].size(); h->x->n32 = (int64_t)cls[1].size(); h->x->n64 = (int64_t)cls[2].size();
     h->x->nh256 = (int64_t)cls[3].size(); h->x->nh1024 = (int64_t)cls[4].size(); h->x->nh4096 = (int64_t)cls[5].size();
     h->x->nh8192 = (int64_t)cls[6].size();
-    if (h->x->nh8192 > 0 && md <= kGiantRow) {
+    if (h->x->nh8192 > 0) {
         // the giant rows' group state: one slice per block of their launches
         h->x->gscratch_blocks = std::min<int64_t>(h->x->nh8192, 64);
         const size_t gb = sizeof(typename BlockGroup<1024, kGiantRow / 1024>::Shared) * (size_t)h->x->gscratch_blocks;
         e = hipMalloc(&h->x->d_gscratch, gb);
         if (e != hipSuccess) return hip_check(h, e, "giant-row scratch");
         h->bytes_allocated += gb;
+    }
+    h->x->nwide = (int64_t)cls[7].size();
+    if (h->x->nwide > 0) {
+        // the wide rows' slices: the longest row rounded up to a tile
+        h->x->wide_blocks = std::min<int64_t>(h->x->nwide, 64);
+        h->x->wide_P = ((int64_t)md + kWideB - 1) / kWideB * kWideB;
+        const size_t wb = (size_t)kWideBytes * (size_t)h->x->wide_P * (size_t)h->x->wide_blocks;
+        e = hipMalloc(&h->x->d_wscratch, wb);
+        if (e != hipSuccess) return hip_check(h, e, "wide-row scratch");
+        h->bytes_allocated += wb;
     }
     if (md > 16 || !h->all_joined || n8 > 0) {   // several classes, or an order by subscriptions: keep the lists
         std::vector<uint32_t> all;
@@ -2600,6 +2631,7 @@ void free_extra(gsim_handle* h)
     if (h->x->d_cany) (void)hipFree(h->x->d_cany);
     if (h->x->d_rows) (void)hipFree(h->x->d_rows);
     if (h->x->d_gscratch) (void)hipFree(h->x->d_gscratch);
+    if (h->x->d_wscratch) (void)hipFree(h->x->d_wscratch);
     if (h->x->d_lastpub) (void)hipFree(h->x->d_lastpub);
     if (h->x->d_fantopics) (void)hipFree(h->x->d_fantopics);
     if (h->x->d_pxo) (void)hipFree(h->x->d_pxo);
@@ -2723,14 +2755,9 @@ static int grid_rows(int64_t n)
     return (int)std::min<int64_t>(std::max<int64_t>(g, 1), 65536);
 }
 
-static int check_degree(gsim_handle* h)
-{
-    if (h->x->max_degree > (uint32_t)kGiantRow) {
-        h->err = "heartbeat kernels support rows of at most 8192 connections in this build";
-        return GSIM_ERANGE;
-    }
-    return GSIM_OK;
-}
+static void launch_heartbeat_wide(gsim_handle* h, const HbArgs& a);
+static void launch_fanout_heartbeat_wide(gsim_handle* h, const HbArgs& a);
+static void launch_fanout_publish_wide(gsim_handle* h, const HbArgs& a, const gsim_msg* d_pub, int32_t count);
 
 uint64_t gsim_get_seed(const gsim_handle* h) { return h->x ? h->x->seed : 0; }
 
@@ -2748,6 +2775,7 @@ int launch_fanout_publish(gsim_handle* h, const gsim_msg* d_pub, int32_t count, 
         hipLaunchKernelGGL((k_fanout_publish_hub_g<1024, kGiantRow / 1024>),
                            dim3((uint32_t)std::min<int64_t>(count, h->x->gscratch_blocks)), dim3(1024), 0, h->stream, a,
                            d_pub, count, 4096u, h->x->d_gscratch);
+    if (h->x->nwide) launch_fanout_publish_wide(h, a, d_pub, count);
     return hip_check(h, hipGetLastError(), "k_fanout_publish");
 }
 
@@ -2765,8 +2793,8 @@ int gsim_heartbeat(gsim_handle* h, uint64_t tick, int64_t now)
     if (!h) return GSIM_EINVAL;
     if (hipSetDevice(h->device) != hipSuccess) return GSIM_EDEVICE;
     if (h->e == 0 || !h->x) { h->err = "no graph loaded"; return GSIM_ESTATE; }
-    int rc = check_degree(h);
-    if (!rc && !h->in_step) rc = deliver_check_errors(h);   // (gsim_step reads them once per call)
+    int rc = GSIM_OK;
+    if (!h->in_step) rc = deliver_check_errors(h);   // (gsim_step reads them once per call)
     if (rc) return rc;
     rc = deliver_flush(h);
     if (!rc) rc = deliver_heartbeat_begin(h, tick);   // IHAVE marks of this heartbeat are pending
@@ -2814,6 +2842,7 @@ int gsim_heartbeat(gsim_handle* h, uint64_t tick, int64_t now)
         if (x->nh8192)   // 8 row positions per thread, group state in global scratch
             hipLaunchKernelGGL((k_heartbeat_hub_g<1024, kGiantRow / 1024>), dim3((uint32_t)x->gscratch_blocks), dim3(1024),
                                0, h->stream, a, rh + x->nh256 + x->nh1024 + x->nh4096, x->nh8192, x->d_gscratch);
+        if (x->nwide) launch_heartbeat_wide(h, a);   // rows over kGiantRow connections, streamed in tiles
     }
     hipLaunchKernelGGL(k_fanout_heartbeat, dim3(grid_rows(nown)), dim3(256), 0, h->stream, a);
     const uint32_t* rh = x->d_rows + x->n16 + x->n32 + x->n64;
@@ -2829,6 +2858,7 @@ int gsim_heartbeat(gsim_handle* h, uint64_t tick, int64_t now)
     if (x->nh8192)
         hipLaunchKernelGGL((k_fanout_heartbeat_hub_g<1024, kGiantRow / 1024>), dim3((uint32_t)x->gscratch_blocks),
                            dim3(1024), 0, h->stream, a, rh + x->nh256 + x->nh1024 + x->nh4096, x->nh8192, x->d_gscratch);
+    if (x->nwide) launch_fanout_heartbeat_wide(h, a);
     if (a.do_px)    // sendGraftPrune's makePrune with PX, live scores after every topic
         launch_px_emit(h, a, 1, (uint32_t)tick, (uint32_t)P_PX);
     return hip_check(h, hipGetLastError(), "k_heartbeat");
@@ -2855,8 +2885,6 @@ int gsim_handle_control(gsim_handle* h, int32_t round, int64_t now)
     if (!h) return GSIM_EINVAL;
     if (hipSetDevice(h->device) != hipSuccess) return GSIM_EDEVICE;
     if (h->e == 0 || !h->x) { h->err = "no graph loaded"; return GSIM_ESTATE; }
-    int rc = check_degree(h);
-    if (rc) return rc;
     return handle_control(h, round, now);
 }
 
@@ -3146,3 +3174,721 @@ extern "C" int gsim_diag_hb_counts(gsim_handle* h, uint64_t* out4)
     return GSIM_OK;
 }
 #endif
+
+// ---------------------------------------------------------------------------
+// Wide rows: more than kGiantRow connections, no upper bound (the reference's
+// heartbeat, fanout maintenance and makePrune have none, gossipsub.go:1386-1596,
+// 1118).  One block of kWideB threads owns one observer and walks its row in
+// tiles: thread tid holds the positions tid, tid + kWideB, ... ("its"
+// positions), and every per-position value of hb_observer lives in the block's
+// slice of global scratch as structure-of-arrays, sized by the row at run time
+// (Extra::wide_P).  Row constants (col, rev, rstate, outbound, direct, the
+// neighbour's subscriptions and slots) are re-read from the row per pass.  A
+// thread reads back what it wrote itself; what crosses threads (the mesh list
+// l*, a position pruned from its list entry, the PX staging) is ordered by
+// __syncthreads().  The semantics are hb_observer's, fanout_observer's and
+// fanout_publish_one's: selection keys depend on row positions and global ids
+// only, so the results are those of every other row class.
+
+namespace {
+
+enum : uint8_t {            // WideRow::bits, per position
+    WB_M = 1,               // in the topic's mesh (fanout kernels: in the fanout)
+    WB_TPEER = 2,           // connected and subscribed to the topic
+    WB_HAVE_BO = 4,         // bo holds the backoff (loaded on first use)
+    WB_BO_DIRTY = 8,
+    WB_SF_HAVE = 16,        // sfv / sfv0 hold the record's score bits (ScoreFlags)
+    WB_CAND = 32,           // candidate of the next selection
+    WB_SEL = 64,            // WideRow::select's result
+    WB_DIRTY = 128          // a Graft / Prune touched a record since the last re-score (lives across topics)
+};
+enum : uint8_t { WC_DUP = 1, WC_HAS1 = 2, WC_HAS2 = 4, WC_GS = 8, WC_REST = 16 };   // WideRow::bits2
+enum : uint8_t { WL_OUTB = 1, WL_TAIL = 2, WL_REST = 4, WL_CB = 8 };                // WideRow::lb, per list entry
+
+struct WideRow {
+    struct Shared {
+        unsigned long long red[2][kWideB / 64];   // reductions (alternating: one barrier each)
+        int ln;
+        double d;
+    };
+    // the slice, P entries each (kWideBytes per position in all)
+    double *S, *Sl;          // snapshot and live score
+    double* lS;              // list: score
+    uint64_t* key;           // selection key (hi << 32 | position; gossip's merge: h1 << 32 | h2)
+    uint64_t* lk;            // list: shuffle key
+    int64_t* bo;
+    int32_t *lq, *lp;        // list: row position, place
+    uint8_t *fl, *fl0, *ctl, *sfv, *sfv0, *bits, *bits2, *lb;
+    Shared* sh;
+    int tid, lane, wid, phase, deg;
+
+    __device__ WideRow(void* scratch, int64_t P, Shared* s)
+        : sh(s), tid((int)threadIdx.x), lane((int)threadIdx.x & 63), wid((int)threadIdx.x >> 6), phase(0), deg(0)
+    {
+        char* p = reinterpret_cast<char*>(scratch) + (int64_t)blockIdx.x * P * kWideBytes;
+        S = reinterpret_cast<double*>(p);
+        Sl = S + P;
+        lS = Sl + P;
+        key = reinterpret_cast<uint64_t*>(lS + P);
+        lk = key + P;
+        bo = reinterpret_cast<int64_t*>(lk + P);
+        lq = reinterpret_cast<int32_t*>(bo + P);
+        lp = lq + P;
+        fl = reinterpret_cast<uint8_t*>(lp + P);
+        fl0 = fl + P; ctl = fl0 + P; sfv = ctl + P; sfv0 = sfv + P; bits = sfv0 + P; bits2 = bits + P; lb = bits2 + P;
+    }
+    __device__ unsigned long long reduce(unsigned long long v, int op)   // 0 sum, 1 min, 2 max (BlockGroup::reduce)
+    {
+        for (int o = 32; o; o >>= 1) {
+            const unsigned long long y = (unsigned long long)__shfl_xor((long long)v, o, 64);
+            v = op == 0 ? v + y : op == 1 ? (y < v ? y : v) : (y > v ? y : v);
+        }
+        unsigned long long* r = sh->red[phase & 1];
+        ++phase;
+        if (lane == 0) r[wid] = v;
+        __syncthreads();
+        unsigned long long acc = r[0];
+        for (int w = 1; w < kWideB / 64; ++w) {
+            const unsigned long long y = r[w];
+            acc = op == 0 ? acc + y : op == 1 ? (y < acc ? y : acc) : (y > acc ? y : acc);
+        }
+        return acc;
+    }
+    // positions whose bits hold all of `all` and none of `none`
+    __device__ int count(uint8_t all, uint8_t none = 0)
+    {
+        unsigned long long c = 0;
+        for (int q = tid; q < deg; q += kWideB) c += (bits[q] & (all | none)) == all;
+        return (int)reduce(c, 0);
+    }
+    __device__ int count2(uint8_t all)
+    {
+        unsigned long long c = 0;
+        for (int q = tid; q < deg; q += kWideB) c += (bits2[q] & all) == all;
+        return (int)reduce(c, 0);
+    }
+    __device__ void set(uint8_t* arr, int q, uint8_t bit, bool on)
+    {
+        arr[q] = on ? (uint8_t)(arr[q] | bit) : (uint8_t)(arr[q] & ~bit);
+    }
+    // BlockGroup::select over the tiles: WB_SEL = the `count` smallest (key,
+    // position) among the positions with `in` (all of them if count <= 0 or
+    // fewer); each adjustment of the tau estimate is one pass over the row
+    __device__ void select(const HbArgs& a, uint8_t in, int count, uint32_t gobs, int32_t t, uint32_t purpose, uint32_t b)
+    {
+        const int n = this->count(in);
+        if (n == 0 || count <= 0 || n <= count) {
+            for (int q = tid; q < deg; q += kWideB) set(bits, q, WB_SEL, n != 0 && (bits[q] & in));
+            return;
+        }
+        const uint32_t tau = (uint32_t)((float)count / (float)n * 4294967040.0f);
+        unsigned long long c0 = 0;
+        for (int q = tid; q < deg; q += kWideB) {
+            const bool cq = bits[q] & in;
+            const uint32_t hi = cq ? hb_key_hi(a, gobs, t, purpose, glob(a, a.col[b + (uint32_t)q]), (uint32_t)q) : 0xFFFFFFFFu;
+            key[q] = ((uint64_t)hi << 32) | (uint32_t)q;
+            const bool sl = cq && hi < tau;
+            set(bits, q, WB_SEL, sl);
+            set(bits2, q, WC_REST, cq && !sl);
+            c0 += sl;
+        }
+        int c = (int)reduce(c0, 0);
+        while (c > count) {                 // drop the largest (key, position) among the selected
+            uint64_t mine = 0;
+            for (int q = tid; q < deg; q += kWideB)
+                if ((bits[q] & WB_SEL) && key[q] > mine) mine = key[q];
+            const uint32_t q = (uint32_t)reduce(mine, 2);
+            if ((int)(q % kWideB) == tid) bits[q] &= (uint8_t)~WB_SEL;
+            --c;
+        }
+        while (c < count) {                 // add the smallest among the others
+            uint64_t mine = ~0ull;
+            for (int q = tid; q < deg; q += kWideB)
+                if ((bits2[q] & WC_REST) && key[q] < mine) mine = key[q];
+            const uint32_t q = (uint32_t)reduce(mine, 1);
+            if ((int)(q % kWideB) == tid) { bits[q] |= WB_SEL; bits2[q] &= (uint8_t)~WC_REST; }
+            ++c;
+        }
+    }
+    // BlockGroup::gossip over the tiles: WC_GS = emitGossip's targets among the
+    // candidates (WB_CAND) and, below Dlo, fill instances of the topic peers
+    __device__ void gossip(const HbArgs& a, uint32_t gobs, int32_t t, uint32_t b)
+    {
+        const int c = count(WB_CAND);
+        for (int q = tid; q < deg; q += kWideB) bits2[q] &= (uint8_t)~(WC_DUP | WC_GS);
+        if (c < a.Dlo) {
+            select(a, WB_TPEER, a.Dlo - c, gobs, t, P_GOSSIP_FILL, b);
+            for (int q = tid; q < deg; q += kWideB) set(bits2, q, WC_DUP, bits[q] & WB_SEL);
+        }
+        const int nd = count2(WC_DUP);
+        const int n = c + nd;
+        if (n == 0) return;
+        int target = a.dlazy;
+        const int factor = (int)(a.gossip_factor * (double)n);
+        if (factor > target) target = factor;
+        if (target >= n) {
+            for (int q = tid; q < deg; q += kWideB) set(bits2, q, WC_GS, (bits[q] & WB_CAND) || (bits2[q] & WC_DUP));
+            return;
+        }
+        if (!nd) {
+            select(a, WB_CAND, target, gobs, t, P_GOSSIP, b);
+            for (int q = tid; q < deg; q += kWideB) set(bits2, q, WC_GS, bits[q] & WB_SEL);
+            return;
+        }
+        // each position holds up to two instances (candidate, fill duplicate)
+        for (int q = tid; q < deg; q += kWideB) {
+            const bool cq = bits[q] & WB_CAND, dq = bits2[q] & WC_DUP;
+            const uint32_t gc = (cq || dq) ? glob(a, a.col[b + (uint32_t)q]) : 0u;
+            const uint32_t h1 = cq ? hb_key_hi(a, gobs, t, P_GOSSIP, gc, (uint32_t)q) : 0xFFFFFFFFu;
+            const uint32_t h2 = dq ? hb_key_hi(a, gobs, t, P_GOSSIP_DUP, gc, (uint32_t)q) : 0xFFFFFFFFu;
+            key[q] = ((uint64_t)h1 << 32) | h2;
+            set(bits2, q, WC_HAS1, cq);
+            set(bits2, q, WC_HAS2, dq);
+        }
+        for (int it = 0; it < target; ++it) {
+            uint64_t mine = ~0ull;
+            for (int q = tid; q < deg; q += kWideB) {
+                const bool has1 = bits2[q] & WC_HAS1, has2 = bits2[q] & WC_HAS2;
+                if (!has1 && !has2) continue;
+                const uint32_t h1 = (uint32_t)(key[q] >> 32), h2 = (uint32_t)key[q];
+                const bool use1 = has1 && (!has2 || h1 <= h2);
+                const uint64_t k = ((uint64_t)(use1 ? h1 : h2) << 32) | (uint32_t)q;
+                if (k < mine) mine = k;
+            }
+            const uint32_t q = (uint32_t)reduce(mine, 1);
+            if ((int)(q % kWideB) == tid) {
+                const bool has1 = bits2[q] & WC_HAS1, has2 = bits2[q] & WC_HAS2;
+                const bool use1 = has1 && (!has2 || (uint32_t)(key[q] >> 32) <= (uint32_t)key[q]);
+                bits2[q] = (uint8_t)((bits2[q] & ~(use1 ? WC_HAS1 : WC_HAS2)) | WC_GS);
+            }
+        }
+    }
+    // The list of the mesh positions (BlockGroup::each): fill(j, q) writes entry
+    // j's values; the entries are in no particular order.  Returns their number.
+    template <class F>
+    __device__ int mesh_list(F fill)
+    {
+        __syncthreads();                    // earlier readers of the list are done
+        if (tid == 0) sh->ln = 0;
+        __syncthreads();
+        for (int q = tid; q < deg; q += kWideB)
+            if (bits[q] & WB_M) {
+                const int j = atomicAdd(&sh->ln, 1);
+                lq[j] = q;
+                fill(j, q);
+            }
+        __syncthreads();
+        return sh->ln;
+    }
+};
+
+// hb_observer restated as passes over the tiles of one wide row
+__device__ __forceinline__ void hb_wide(const HbArgs& a, WideRow& g, int64_t obs)
+{
+    const int tid = g.tid;
+    const uint32_t b = a.row_ptr[obs];
+    const int deg = (int)(a.row_ptr[obs + 1] - b);
+    g.deg = deg;
+    const uint32_t gobs = glob(a, (uint32_t)obs);
+    const uint64_t subi = a.sub[obs];
+    const uint64_t mi = smask_of(a.smask, (uint32_t)obs);
+    const bool traced = a.tr.on((uint32_t)obs);
+    for (int q = tid; q < deg; q += kWideB) {
+        const uint32_t e = b + (uint32_t)q;
+        const double s = a.score[a.rev[e]];
+        g.S[q] = s;
+        g.Sl[q] = s;
+        g.bits[q] = 0;
+        if (a.gossip) a.gstate[e] = s >= a.gossip_thr ? 1 : 0;
+    }
+    uint64_t pxt = 0;                               // topics with a PRUNE carrying PX
+    auto rescore = [&]() {                          // live scores of the dirty positions
+        if (g.count(WB_DIRTY)) {
+            for (int q = tid; q < deg; q += kWideB)
+                if (g.bits[q] & WB_DIRTY) {
+                    const uint32_t e = b + (uint32_t)q;
+                    g.Sl[q] = score_of_record(a, a.rev[e], a.col[e]);
+                    g.bits[q] &= (uint8_t)~WB_DIRTY;
+                }
+        }
+    };
+
+    // clearBackoff every 15 ticks (gossipsub.go:1627-1646)
+    if (a.tick % 15 == 0) {
+        for (int q = tid; q < deg; q += kWideB)
+            for (int32_t t = 0; t < a.T; ++t) {
+                if (!slot_has(mi, t)) continue;
+                const int64_t i = slot_idx(mi, t, a.E, b + (uint32_t)q);
+                const int64_t bo = a.backoff[i];
+                if (bo != 0 && bo + kBackoffSlack < a.now) a.backoff[i] = 0;
+            }
+    }
+
+    for (int32_t t = 0; t < a.T; ++t) {
+        if (!((subi >> t) & 1ull)) continue;           // not joined
+        const ctp_t tp = const_tp(a.tp) + t;
+        const bool scored = tp->scored != 0;
+        const double thr = tp->mesh_message_deliveries_threshold;
+        const double mcap = tp->mesh_message_deliveries_cap;
+        for (int q = tid; q < deg; q += kWideB) {
+            const uint32_t e = b + (uint32_t)q;
+            const uint8_t fl = a.mflags[slot_idx(mi, t, a.E, e)];
+            g.fl[q] = fl;
+            g.fl0[q] = fl;
+            g.ctl[q] = 0;
+            const bool conn = a.rstate[e] & GSIM_ES_CONNECTED;
+            const bool tpeer = conn && (a.sub_all || ((a.sub[a.col[e]] >> t) & 1ull));
+            g.bits[q] = (uint8_t)((g.bits[q] & WB_DIRTY) | ((fl & GSIM_TF_MESH) ? WB_M : 0) | (tpeer ? WB_TPEER : 0));
+        }
+        auto need_bo = [&](int q) {
+            if (!(g.bits[q] & WB_HAVE_BO)) {
+                g.bo[q] = a.backoff[slot_idx(mi, t, a.E, b + (uint32_t)q)];
+                g.bits[q] |= WB_HAVE_BO;
+            }
+        };
+        // the record's score bits around a Graft / Prune (ScoreFlags kept in the slice)
+        auto with_sf = [&](int q, uint32_t col, uint32_t rv, auto f) {
+            ScoreFlags sf;
+            sf.at(smask_of(a.smask, col), t, a.E, rv);
+            sf.have = g.bits[q] & WB_SF_HAVE;
+            sf.v = g.sfv[q];
+            sf.v0 = g.sfv0[q];
+            f(sf);
+            if (sf.have) {
+                g.bits[q] |= WB_SF_HAVE;
+                g.sfv[q] = sf.v;
+                g.sfv0[q] = sf.v0;
+            }
+        };
+        auto prune = [&](int q) {
+            const uint32_t e = b + (uint32_t)q, col = a.col[e], rv = a.rev[e];
+            const bool tracked = a.estate[rv] & GSIM_ES_TRACKED;
+            if (traced) a.tr.push(a.now, 0, (uint32_t)obs, col, t, GSIM_TRACE_PRUNE, 0);
+            with_sf(q, col, rv, [&](ScoreFlags& sf) { stats_prune(a, tracked, scored, thr, mcap, sf); });
+            if (tracked && scored) g.bits[q] |= WB_DIRTY;
+            g.fl[q] &= (uint8_t)~GSIM_TF_MESH;
+            g.bits[q] &= (uint8_t)~WB_M;
+            need_bo(q);
+            const int64_t ex = a.now + a.prune_backoff;
+            if (g.bo[q] < ex) { g.bo[q] = ex; g.bits[q] |= WB_BO_DIRTY; }
+            g.ctl[q] |= GSIM_CTL_PRUNE;
+        };
+        auto graft = [&](int q) {
+            const uint32_t e = b + (uint32_t)q, col = a.col[e], rv = a.rev[e];
+            const bool tracked = a.estate[rv] & GSIM_ES_TRACKED;
+            if (traced) a.tr.push(a.now, 0, (uint32_t)obs, col, t, GSIM_TRACE_GRAFT, 0);
+            with_sf(q, col, rv, [&](ScoreFlags& sf) { stats_graft(a, tracked, scored, sf); });
+            if (tracked && scored) g.bits[q] |= WB_DIRTY;
+            g.fl[q] |= GSIM_TF_MESH;
+            g.bits[q] |= WB_M;
+            g.ctl[q] |= GSIM_CTL_GRAFT;
+        };
+        auto graft_selected = [&]() {
+            for (int q = tid; q < deg; q += kWideB)
+                if (g.bits[q] & WB_SEL) graft(q);
+        };
+
+        // drop all peers with negative score (1403-1410)
+        for (int q = tid; q < deg; q += kWideB)
+            if ((g.bits[q] & WB_M) && g.S[q] < 0) prune(q);
+
+        // too few peers: graft up to D (1412-1427)
+        int l = g.count(WB_M);
+        if (l < a.Dlo) {
+            for (int q = tid; q < deg; q += kWideB) {
+                need_bo(q);
+                const uint8_t x = g.bits[q];
+                g.set(g.bits, q, WB_CAND, (x & WB_TPEER) && !(x & WB_M) && g.bo[q] == 0 && !a.direct[b + (uint32_t)q] &&
+                                              g.S[q] >= 0);
+            }
+            g.select(a, WB_CAND, a.D - l, gobs, t, P_GRAFT_DLO, b);
+            graft_selected();
+        }
+
+        // too many peers: keep Dscore best + random, Dout outbound (1429-1490);
+        // every rank is taken over the list of the mesh positions
+        l = g.count(WB_M);
+        if (l > a.Dhi) {
+            const int n = g.mesh_list([&](int j, int q) {
+                const uint32_t e = b + (uint32_t)q;
+                g.lS[j] = g.S[q];
+                g.lk[j] = hb_key(a, gobs, t, P_PRUNE_SHUF1, glob(a, a.col[e]), (uint32_t)q);
+                g.lb[j] = a.outbound[e] ? WL_OUTB : 0;
+            });
+            const int ds = a.Dscore < l ? a.Dscore : l;
+            for (int j = tid; j < n; j += kWideB) {
+                const double sj = g.lS[j];
+                const uint64_t kj = g.lk[j];
+                int r = 0;
+                for (int i = 0; i < n; ++i) {
+                    const double si = g.lS[i];
+                    r += si > sj || (si == sj && g.lk[i] < kj);
+                }
+                g.lp[j] = r;
+            }
+            __syncthreads();                    // the rank loops are done with the first keys
+            for (int j = tid; j < n; j += kWideB) {
+                const bool tail = g.lp[j] >= ds;
+                const int q = g.lq[j];
+                g.lk[j] = tail ? hb_key(a, gobs, t, P_PRUNE_SHUF2, glob(a, a.col[b + (uint32_t)q]), (uint32_t)q) : ~0ull;
+                if (tail) g.lb[j] |= WL_TAIL;
+            }
+            __syncthreads();
+            unsigned long long obc = 0;
+            for (int j = tid; j < n; j += kWideB) {
+                if (g.lb[j] & WL_TAIL) {
+                    const uint64_t kj = g.lk[j];
+                    int below = 0;
+                    for (int i = 0; i < n; ++i) below += g.lk[i] < kj;   // non-tail entries hold ~0 and never count
+                    g.lp[j] = ds + below;
+                }
+                obc += g.lp[j] < a.D && (g.lb[j] & WL_OUTB);
+            }
+            // Keep plst[:D] after Go's Dout rotation (1457-1485), from each entry's
+            // place p in plst (hb_observer)
+            const int obD = (int)g.reduce(obc, 0);
+            const bool rot = obD < a.Dout;
+            int jj = 0;
+            if (rot) {
+                unsigned long long nbc = 0;
+                for (int j = tid; j < n; j += kWideB) {
+                    const int p = g.lp[j];
+                    const bool outb = g.lb[j] & WL_OUTB, inD = p < a.D;
+                    const bool rest = inD && !(outb && p >= 1), cb = p >= a.D && outb;
+                    g.lb[j] = (uint8_t)(g.lb[j] | (rest ? WL_REST : 0) | (cb ? WL_CB : 0));
+                    nbc += cb;
+                }
+                const int nb = (int)g.reduce(nbc, 0);
+                jj = a.Dout - obD < nb ? a.Dout - obD : nb;
+            }
+            for (int j = tid; j < n; j += kWideB) {
+                const int p = g.lp[j];
+                const bool inD = p < a.D;
+                bool keep = inD;
+                if (rot) {
+                    const bool rest = g.lb[j] & WL_REST, cb = g.lb[j] & WL_CB;
+                    int rb = 0, rr = 0;
+                    if (rest || cb)
+                        for (int i = 0; i < n; ++i) {
+                            const int pi = g.lp[i];
+                            const uint8_t bi = g.lb[i];
+                            rb += (bi & WL_CB) && pi < p;
+                            rr += (bi & WL_REST) && pi > p;
+                        }
+                    keep = (inD && !(rest && rr < jj)) || (cb && rb < jj);
+                }
+                if (!keep) {                    // (the entry's thread, not the position's: ordered by the barrier below)
+                    const int q = g.lq[j];
+                    prune(q);
+                    if (a.do_px) g.ctl[q] |= GSIM_CTL_PX;     // makePrune(p, topic, doPX && !noPX[p]) (1690)
+                }
+            }
+            __syncthreads();
+        }
+
+        // enough outbound peers? (1492-1518)
+        l = g.count(WB_M);
+        if (l >= a.Dlo) {
+            unsigned long long oc = 0;
+            for (int q = tid; q < deg; q += kWideB) oc += (g.bits[q] & WB_M) && a.outbound[b + (uint32_t)q];
+            const int ob = (int)g.reduce(oc, 0);
+            if (ob < a.Dout) {
+                for (int q = tid; q < deg; q += kWideB) {
+                    need_bo(q);
+                    const uint8_t x = g.bits[q];
+                    const uint32_t e = b + (uint32_t)q;
+                    g.set(g.bits, q, WB_CAND, (x & WB_TPEER) && !(x & WB_M) && g.bo[q] == 0 && !a.direct[e] &&
+                                                  a.outbound[e] && g.S[q] >= 0);
+                }
+                g.select(a, WB_CAND, a.Dout - ob, gobs, t, P_GRAFT_DOUT, b);
+                graft_selected();
+            }
+        }
+
+        // opportunistic grafting (1520-1552)
+        l = g.count(WB_M);
+        if (a.opp_ticks && a.tick % a.opp_ticks == 0 && l > 1) {
+            const int n = g.mesh_list([&](int j, int q) { g.lS[j] = g.S[q]; });
+            for (int j = tid; j < n; j += kWideB) {
+                const double sj = g.lS[j];
+                const int qj = g.lq[j];
+                int r = 0;
+                for (int i = 0; i < n; ++i) {
+                    const double si = g.lS[i];
+                    r += si < sj || (si == sj && g.lq[i] < qj);
+                }
+                if (r == l / 2) g.sh->d = sj;   // the ranks are a permutation: one entry
+            }
+            __syncthreads();
+            const double median = g.sh->d;
+            if (median < a.opp_threshold) {
+                for (int q = tid; q < deg; q += kWideB) {
+                    need_bo(q);
+                    const uint8_t x = g.bits[q];
+                    g.set(g.bits, q, WB_CAND, (x & WB_TPEER) && !(x & WB_M) && g.bo[q] == 0 && !a.direct[b + (uint32_t)q] &&
+                                                  g.S[q] > median);
+                }
+                g.select(a, WB_CAND, a.opp_peers, gobs, t, P_GRAFT_OPP, b);
+                graft_selected();
+            }
+        }
+
+        for (int q = tid; q < deg; q += kWideB) {
+            const uint32_t e = b + (uint32_t)q;
+            const int64_t i = slot_idx(mi, t, a.E, e);
+            if (g.fl[q] != g.fl0[q]) a.mflags[i] = g.fl[q];
+            if (g.bits[q] & WB_SF_HAVE) {
+                ScoreFlags sf;
+                sf.at(smask_of(a.smask, a.col[e]), t, a.E, a.rev[e]);
+                sf.have = true;
+                sf.v = g.sfv[q];
+                sf.v0 = g.sfv0[q];
+                sf.store(a);
+            }
+            if (g.bits[q] & WB_BO_DIRTY) a.backoff[i] = g.bo[q];
+        }
+
+        // emitGossip(topic, mesh) (gossipsub.go:1554-1556, 1711-1775), as hb_observer
+        if (a.gossip) {
+            const int32_t lpt = a.lastput[(int64_t)t * a.N + obs];
+            const bool emit = lpt >= 0 && lpt >= (int64_t)a.tick - a.hist_gossip;   // -1: no put yet
+            if (emit) {
+                rescore();
+                for (int q = tid; q < deg; q += kWideB) {
+                    const uint8_t x = g.bits[q];
+                    g.set(g.bits, q, WB_CAND, (x & WB_TPEER) && !(x & WB_M) && !a.direct[b + (uint32_t)q] &&
+                                                  g.Sl[q] >= a.gossip_thr);
+                }
+                g.gossip(a, gobs, t, b);
+            }
+            for (int q = tid; q < deg; q += kWideB)
+                a.gsel[slot_idx(mi, t, a.E, b + (uint32_t)q)] = emit && (g.bits2[q] & WC_GS) ? 1 : 0;
+        }
+        unsigned long long pxc = 0;
+        for (int q = tid; q < deg; q += kWideB) {
+            const uint8_t c = g.ctl[q];
+            if (!c) continue;
+            const uint32_t e = b + (uint32_t)q, col = a.col[e];
+            const uint64_t mj = smask_of(a.smask, col);
+            if (slot_has(mj, t)) {
+                const int64_t r = slot_idx(mj, t, a.E, a.rev[e]);   // the receiver's row
+                a.ctl_out[r] = (uint8_t)(a.ctl_out[r] | c);
+                atomicOr(reinterpret_cast<unsigned long long*>(a.cany_out + col), 1ull << t);
+            }
+            pxc += (c & GSIM_CTL_PX) != 0;
+        }
+        if (a.do_px && g.reduce(pxc, 0)) pxt |= 1ull << t;
+    }
+    // sendGraftPrune follows every topic: k_px_emit_wide picks the PX peers
+    if (a.do_px && pxt) {
+        rescore();
+        for (int q = tid; q < deg; q += kWideB) a.pxs[b + (uint32_t)q] = g.Sl[q];
+        if (tid == 0) a.pxo[obs] = pxt;
+    }
+}
+
+// fanout_observer over the tiles of one wide row (WB_M: in the fanout)
+__device__ __forceinline__ void fanout_wide(const HbArgs& a, WideRow& g, int64_t obs)
+{
+    const int tid = g.tid;
+    const int64_t lpub = tid < a.T ? a.lastpub[obs * a.T + tid] : 0;   // thread t < 64: topic t
+    const bool ex = lpub != 0 && lpub + a.fanout_ttl < a.now;
+    const uint64_t expired = g.reduce(tid < 64 ? (uint64_t)ex << tid : 0ull, 0);
+    const uint64_t fant0 = a.fan_topics[obs];
+    if (!expired && !fant0) return;                         // block-uniform
+    const uint32_t b = a.row_ptr[obs];
+    const int deg = (int)(a.row_ptr[obs + 1] - b);
+    g.deg = deg;
+    if (tid < 64 && ((expired >> tid) & 1ull)) a.lastpub[obs * a.T + tid] = 0;
+    const uint64_t mi = smask_of(a.smask, (uint32_t)obs);   // fanout topics hold slots (gsim_publish)
+    for (uint64_t m = expired & fant0 & mi; m; m &= m - 1)
+        for (int q = tid; q < deg; q += kWideB) {
+            const int64_t i = slot_idx(mi, __ffsll((long long)m) - 1, a.E, b + (uint32_t)q);
+            const uint8_t fl = a.mflags[i];
+            if (fl & GSIM_TF_FANOUT) a.mflags[i] = (uint8_t)(fl & ~GSIM_TF_FANOUT);
+            if (a.gossip) a.gsel[i] = 0;                    // no more gossip for it
+        }
+    const uint64_t fant = fant0 & ~expired;
+    __syncthreads();                                        // every thread has read fan_topics
+    if (tid == 0 && fant != fant0) a.fan_topics[obs] = fant;
+    if (!fant) return;
+    const uint32_t gobs = glob(a, (uint32_t)obs);
+    for (int q = tid; q < deg; q += kWideB) g.S[q] = a.score[a.rev[b + (uint32_t)q]];
+    bool have_live = false;
+    for (uint64_t m = fant & mi; m; m &= m - 1) {
+        const int32_t t = __ffsll((long long)m) - 1;
+        for (int q = tid; q < deg; q += kWideB) {
+            const uint32_t e = b + (uint32_t)q;
+            const uint8_t fl = a.mflags[slot_idx(mi, t, a.E, e)];
+            g.fl[q] = fl;
+            const bool conn = a.rstate[e] & GSIM_ES_CONNECTED;
+            const bool tpeer = conn && (a.sub_all || ((a.sub[a.col[e]] >> t) & 1ull));
+            const bool inf = (fl & GSIM_TF_FANOUT) && tpeer && g.S[q] >= a.pub_thr;
+            g.bits[q] = (uint8_t)((inf ? WB_M : 0) | (tpeer ? WB_TPEER : 0));
+        }
+        const int have = g.count(WB_M);
+        if (have < a.D) {
+            for (int q = tid; q < deg; q += kWideB) {
+                const uint8_t x = g.bits[q];
+                g.set(g.bits, q, WB_CAND, (x & WB_TPEER) && !(x & WB_M) && !a.direct[b + (uint32_t)q] && g.S[q] >= a.pub_thr);
+            }
+            g.select(a, WB_CAND, a.D - have, gobs, t, P_FANOUT, b);
+            for (int q = tid; q < deg; q += kWideB)
+                if (g.bits[q] & WB_SEL) g.bits[q] |= WB_M;
+        }
+        for (int q = tid; q < deg; q += kWideB) {
+            const uint8_t fl = g.fl[q];
+            const uint8_t nf = (g.bits[q] & WB_M) ? (uint8_t)(fl | GSIM_TF_FANOUT) : (uint8_t)(fl & ~GSIM_TF_FANOUT);
+            if (nf != fl) a.mflags[slot_idx(mi, t, a.E, b + (uint32_t)q)] = nf;
+        }
+        if (!a.gossip) continue;
+        const int32_t lpt = a.lastput[(int64_t)t * a.N + obs];
+        const bool emit = lpt >= 0 && lpt >= (int64_t)a.tick - a.hist_gossip;
+        if (emit) {
+            if (!have_live) {                               // live Score(p), gossipsub.go:1734
+                for (int q = tid; q < deg; q += kWideB) {
+                    const uint32_t e = b + (uint32_t)q;
+                    g.Sl[q] = score_of_record(a, a.rev[e], a.col[e]);
+                }
+                have_live = true;
+            }
+            for (int q = tid; q < deg; q += kWideB) {
+                const uint8_t x = g.bits[q];
+                g.set(g.bits, q, WB_CAND, (x & WB_TPEER) && !(x & WB_M) && !a.direct[b + (uint32_t)q] &&
+                                              g.Sl[q] >= a.gossip_thr);
+            }
+            g.gossip(a, gobs, t, b);
+        }
+        for (int q = tid; q < deg; q += kWideB)
+            a.gsel[slot_idx(mi, t, a.E, b + (uint32_t)q)] = emit && (g.bits2[q] & WC_GS) ? 1 : 0;
+    }
+}
+
+// fanout_publish_one over the tiles of a wide origin's row
+__device__ __forceinline__ void fanout_publish_wide(const HbArgs& a, WideRow& g, const gsim_msg* pub, int32_t k)
+{
+    const int tid = g.tid;
+    const uint32_t o = pub[k].origin;
+    const int32_t t = (int32_t)pub[k].topic;
+    unsigned long long dup = 0;
+    for (int32_t q = tid; q < k; q += kWideB) dup += pub[q].origin == o && (int32_t)pub[q].topic == t;
+    if (g.reduce(dup, 0)) return;                  // an earlier message of the batch did the selection
+    const uint32_t b = a.row_ptr[o];
+    const int deg = (int)(a.row_ptr[o + 1] - b);
+    g.deg = deg;
+    const uint64_t mo = smask_of(a.smask, o);      // gsim_publish gave the origin a slot for t
+    if (!slot_has(mo, t)) return;                  // block-uniform
+    for (int q = tid; q < deg; q += kWideB) {
+        const uint8_t fl = a.mflags[slot_idx(mo, t, a.E, b + (uint32_t)q)];
+        g.fl[q] = fl;
+        g.bits[q] = (fl & GSIM_TF_FANOUT) ? WB_M : 0;
+    }
+    const uint64_t fan = a.fan_topics[o];
+    const bool have = g.count(WB_M) != 0 && ((fan >> t) & 1ull);   // (every thread has read fan_topics: the barrier)
+    if (!have) {
+        for (int q = tid; q < deg; q += kWideB) {
+            const uint32_t e = b + (uint32_t)q;
+            const bool conn = a.rstate[e] & GSIM_ES_CONNECTED;
+            const bool tpeer = conn && ((a.sub[a.col[e]] >> t) & 1ull);
+            g.set(g.bits, q, WB_CAND, tpeer && !(g.bits[q] & WB_M) && !a.direct[e] && a.score[a.rev[e]] >= a.pub_thr);
+        }
+        g.select(a, WB_CAND, a.D, glob(a, o), t, P_FANOUT_NEW, b);
+        for (int q = tid; q < deg; q += kWideB)
+            if (g.bits[q] & WB_SEL) a.mflags[slot_idx(mo, t, a.E, b + (uint32_t)q)] = (uint8_t)(g.fl[q] | GSIM_TF_FANOUT);
+        const bool any = g.count(WB_SEL) != 0;
+        if (tid == 0 && any) atomicOr(reinterpret_cast<unsigned long long*>(a.fan_topics + o), 1ull << t);
+    }
+    if (tid == 0) a.lastpub[(int64_t)o * a.T + t] = a.now;
+}
+
+}  // namespace
+
+// HbArgs first: score_of_record re-reads it from the kernarg segment (hb_launder)
+__global__ __launch_bounds__(kWideB) void k_heartbeat_wide(HbArgs a, const uint32_t* rows, int64_t nrows, void* scratch,
+                                                           int64_t P)
+{
+    __shared__ WideRow::Shared sh;
+    WideRow g(scratch, P, &sh);
+    for (int64_t o = blockIdx.x; o < nrows; o += gridDim.x) {
+        hb_wide(a, g, (int64_t)rows[o]);
+        __syncthreads();                        // the slice is rewritten by the next observer
+    }
+}
+
+__global__ __launch_bounds__(kWideB) void k_fanout_heartbeat_wide(HbArgs a, const uint32_t* rows, int64_t nrows,
+                                                                  void* scratch, int64_t P)
+{
+    __shared__ WideRow::Shared sh;
+    WideRow g(scratch, P, &sh);
+    for (int64_t o = blockIdx.x; o < nrows; o += gridDim.x) {
+        fanout_wide(a, g, (int64_t)rows[o]);
+        __syncthreads();
+    }
+}
+
+// origins with rows of more than kGiantRow connections: the grid strides over
+// the batch (one scratch slice per block)
+__global__ __launch_bounds__(kWideB) void k_fanout_publish_wide(HbArgs a, const gsim_msg* pub, int32_t count,
+                                                                void* scratch, int64_t P)
+{
+    __shared__ WideRow::Shared sh;
+    WideRow g(scratch, P, &sh);
+    for (int32_t k = (int32_t)blockIdx.x; k < count; k += (int32_t)gridDim.x) {
+        if (!fanout_publisher(a, pub, k)) continue;      // block-uniform
+        const uint32_t o = pub[k].origin;
+        if (a.row_ptr[o + 1] - a.row_ptr[o] <= (uint32_t)kGiantRow) continue;
+        fanout_publish_wide(a, g, pub, k);
+        __syncthreads();
+    }
+}
+
+// makePrune's PX lists of the wide rows: k_px_emit's hub body with the
+// observer's scores, the topic's candidate bits and their draws in the block's
+// scratch slice instead of LDS (S, key and lq of WideRow: the heartbeat is done
+// with them).  A PRUNE's list costs a pass over the row and a hub prunes
+// thousands, so the block is kWideB threads: 16 waves take the PRUNEs in turn.
+constexpr int kPxWideWaves = kWideB / 64;
+__global__ __launch_bounds__(kWideB) void k_px_emit_wide(HbArgs a, int live, uint32_t key_tick, uint32_t purpose,
+                                                         const uint32_t* rows, int64_t nrows, void* scratch, int64_t P)
+{
+    __shared__ uint64_t s_lst[kPxWideWaves][kPxList];            // a PRUNE's smallest keys
+    char* p = reinterpret_cast<char*>(scratch) + (int64_t)blockIdx.x * P * kWideBytes;
+    double* sc = reinterpret_cast<double*>(p);                                   // [P]
+    uint64_t* cb = reinterpret_cast<uint64_t*>(p + 8 * P);                       // [P / 64]
+    uint32_t* pb = reinterpret_cast<uint32_t*>(p + 16 * P);                      // [P]
+    px_emit_rows<0x7FFFFFFF, kPxWideWaves, true>(a, live, key_tick, purpose, rows, nrows, sc, cb, pb,
+                                                 s_lst[threadIdx.x >> 6]);
+}
+
+static const uint32_t* wide_rows(const Extra* x)
+{
+    return x->d_rows + x->n16 + x->n32 + x->n64 + x->nh256 + x->nh1024 + x->nh4096 + x->nh8192;
+}
+
+static void launch_heartbeat_wide(gsim_handle* h, const HbArgs& a)
+{
+    const Extra* x = h->x;
+    hipLaunchKernelGGL(k_heartbeat_wide, dim3((uint32_t)x->wide_blocks), dim3(kWideB), 0, h->stream, a, wide_rows(x),
+                       x->nwide, x->d_wscratch, x->wide_P);
+}
+
+static void launch_fanout_heartbeat_wide(gsim_handle* h, const HbArgs& a)
+{
+    const Extra* x = h->x;
+    hipLaunchKernelGGL(k_fanout_heartbeat_wide, dim3((uint32_t)x->wide_blocks), dim3(kWideB), 0, h->stream, a,
+                       wide_rows(x), x->nwide, x->d_wscratch, x->wide_P);
+}
+
+static void launch_fanout_publish_wide(gsim_handle* h, const HbArgs& a, const gsim_msg* d_pub, int32_t count)
+{
+    const Extra* x = h->x;
+    hipLaunchKernelGGL(k_fanout_publish_wide, dim3((uint32_t)std::min<int64_t>(count, x->wide_blocks)), dim3(kWideB), 0,
+                       h->stream, a, d_pub, count, x->d_wscratch, x->wide_P);
+}
+
+static void launch_px_emit_wide(gsim_handle* h, const HbArgs& a, int live, uint32_t key_tick, uint32_t purpose)
+{
+    const Extra* x = h->x;
+    hipLaunchKernelGGL(k_px_emit_wide, dim3((uint32_t)x->wide_blocks), dim3(kWideB), 0, h->stream, a, live, key_tick, purpose,
+                       wide_rows(x), x->nwide, x->d_wscratch, x->wide_P);
+}

@@ -180,7 +180,9 @@ const char* gsim_last_error(const gsim_handle* h);
  * ip_ptr/ip_ids = per-peer CSR of IP ids as seen by its neighbours
  * (score.go:984-1024 getIPs; IPv6 /64 prefixes are just more ids).
  * Every edge starts tracked+connected (AddPeer, score.go:595-609) with zero
- * counters, nothing in any mesh.  Copies everything. */
+ * counters, nothing in any mesh.  Copies everything.  No row limit applies:
+ * a peer may hold any number of connections (the reference has no degree
+ * bound); the one bound is the uint32 edge index, E < 2^32. */
 int gsim_load_graph(gsim_handle* h, int64_t n_peers,
                     const uint32_t* row_ptr, const uint32_t* col_idx,
                     const uint8_t* outbound, const uint64_t* subscriptions,
@@ -227,7 +229,9 @@ int gsim_set_seed(gsim_handle* h, uint64_t seed);
  * every OpportunisticGraftTicks; Graft/Prune traced into the score counters.
  * Uses the current score snapshot as the heartbeat's score cache
  * (gossipsub.go:1375-1383): call gsim_refresh_scores first.  GRAFT/PRUNE
- * records land in the receivers' control inbox for round 0.  Fails with the
+ * records land in the receivers' control inbox for round 0.  No row limit
+ * applies (rows of any length; the longest run on kernels that stream the row
+ * in tiles).  Fails with the
  * previous tick's delivery error, if any (GSIM_ERANGE: the IWANT response
  * queue overflowed; GSIM_ESTATE: a slot was republished too early). */
 int gsim_heartbeat(gsim_handle* h, uint64_t tick, int64_t now_ns);
