@@ -776,6 +776,18 @@ __device__ __forceinline__ uint32_t kth_bit(uint64_t m, uint32_t k)
     return pos;
 }
 
+// The end of a batch of loads issued back to back: the values are consumed here
+// (an empty statement the compiler cannot see through), so no load is sunk into
+// the branch that uses it, behind another load's wait.
+__device__ __forceinline__ void loads_done(uint32_t& v) { asm volatile("" : "+v"(v)); }
+__device__ __forceinline__ void loads_done(uint64_t& v) { asm volatile("" : "+v"(v)); }
+template <class T, class... R>
+__device__ __forceinline__ void loads_done(T& v, R&... r)
+{
+    loads_done(v);
+    loads_done(r...);
+}
+
 // The mesh masks of rows of at most 64 connections: bit q of mmask[t][x] =
 // position q of row x carries the router's mesh bit for t, or is a direct
 // peer; only edges to the receivers [rlo, rhi) (a shard's owned peers).
@@ -830,7 +842,9 @@ __global__ __launch_bounds__(256) void k_hub_mesh(const uint32_t* row_ptr, const
             const uint32_t i = v ? col[e] : 0u;
             const bool own = v && i >= rlo && i < rhi;
             const bool dr = own && direct && direct[e];
-            for (uint64_t mm = m; mm;) {
+            // (an all-joined network has no slot masks, m = ~0: only the T topics exist --
+            // walking bits T..63 read flag planes and wrote lists that are not there)
+            for (uint64_t mm = T < 64 ? m & ((1ull << T) - 1ull) : m; mm;) {
                 int tb[kHubBatch];
                 uint8_t fb[kHubBatch];
 #pragma unroll
@@ -897,7 +911,10 @@ __global__ __launch_bounds__(256) void k_hub_index(const uint32_t* row_ptr, int6
 // and hubs their whole row.
 constexpr int kTsSlots = 64;
 #ifndef GSIM_TM_P
-#define GSIM_TM_P 2          // flattened edges per thread per iteration (loads interleaved)
+// flattened edges (copies) per thread per iteration: the iteration runs in phases
+// over all of them -- row state, committed bit, cell, stores -- each phase's loads
+// or atomics issued back to back with one wait, three dependent trips for P copies
+#define GSIM_TM_P 2
 #endif
 #ifndef GSIM_TM_MINB
 #define GSIM_TM_MINB 1       // waves per SIMD the register budget is fitted to
@@ -1114,22 +1131,71 @@ void k_send_tm(RoundArgs a_)
                 const uint32_t fb = (pm[0] ? 1u : 0u) | (pm[1] ? 2u : 0u);
                 uint32_t len2[2] = {0, 0}, beg2[2] = {0, 0}, from2[2] = {0, 0}, k2[2] = {0, 0}, pl2[2] = {0, 0};
                 uint64_t msk2[2] = {0, 0};
+                // Both peers' loads go out together, one wait for all of them: the
+                // addresses are formed first (a lane without a forwarder reads the
+                // block's first peer, always valid), the results selected afterwards.
+                uint32_t x2[2];
+                int64_t xc2[2];
+                uint64_t xm2[2] = {~0ull, ~0ull};
+#pragma unroll
+                for (int u = 0; u < 2; ++u) {
+                    const bool on = (fb >> u) & 1u;
+                    k2[u] = on ? (uint32_t)__builtin_ctzll(pm[u]) : 0u;
+                    x2[u] = on ? (uint32_t)(x0 + u) : (uint32_t)lo;
+                    xc2[u] = (int64_t)s_m[k2[u]] * a.cs.n + x2[u];
+                }
+                if constexpr (SP) {
+                    // the member tables and slot masks come first: one trip for both peers
+                    uint64_t tb[2] = {~0ull, ~0ull};
+                    uint32_t tpre[2];
+                    const bool spt = (a.cs.sparse >> t) & 1ull;
+#pragma unroll
+                    for (int u = 0; u < 2; ++u) {
+                        tpre[u] = (x2[u] >> 6) * 64u;
+                        if (spt) {
+                            const int64_t wi_ = (int64_t)t * a.cs.nw + (x2[u] >> 6);
+                            tb[u] = a.cs.mbits[wi_];
+                            tpre[u] = a.cs.mpre[wi_];
+                        }
+                        if (a.smask) xm2[u] = a.smask[x2[u]];
+                    }
+                    loads_done(tb[0], tb[1], tpre[0], tpre[1], xm2[0], xm2[1]);
+#pragma unroll
+                    for (int u = 0; u < 2; ++u) {
+                        const uint64_t bit = 1ull << (x2[u] & 63);
+                        const int64_t cb = (int64_t)s_cb[k2[u]];
+                        xc2[u] = (tb[u] & bit) ? cb + tpre[u] + __popcll(tb[u] & (bit - 1)) : -1;
+                    }
+                }
+                uint64_t cell2[2], mm2[2];
+                uint32_t rb2[2], re2[2];
+#pragma unroll
+                for (int u = 0; u < 2; ++u) {
+                    cell2[u] = 0;
+                    if constexpr (SP) {
+                        if (xc2[u] >= 0) cell2[u] = a.cs.cell[xc2[u]];   // (a fanout origin holds no cell)
+                    } else {
+                        cell2[u] = a.cs.cell[xc2[u]];
+                    }
+                    rb2[u] = a.row_ptr[x2[u]];
+                    re2[u] = a.row_ptr[x2[u] + 1];
+                    mm2[u] = a.mmask[(int64_t)t * a.N + x2[u]];
+                }
+                loads_done(cell2[0], cell2[1], rb2[0], rb2[1], re2[0], re2[1], mm2[0], mm2[1]);
 #pragma unroll
                 for (int u = 0; u < 2; ++u) {
                     if ((fb >> u) & 1u) {
-                        k2[u] = (uint32_t)__builtin_ctzll(pm[u]);
-                        const uint32_t x = (uint32_t)(x0 + u), m = s_m[k2[u]];
+                        const uint32_t x = x2[u];
                         // a forwarder's cell (committed)
-                        const int64_t xc = SP ? a.cs.at((int64_t)s_cb[k2[u]], t, x) : (int64_t)m * a.cs.n + x;
-                        from2[u] = xc >= 0 ? (uint32_t)a.cs.cell[xc] & kPeerMask : kPeerMask;
-                        const uint64_t xm = SP ? smask_of(a.smask, x) : ~0ull;
+                        from2[u] = xc2[u] >= 0 ? (uint32_t)cell2[u] & kPeerMask : kPeerMask;
+                        const uint64_t xm = xm2[u];
                         pl2[u] = (uint32_t)__popcll(xm & ((1ull << t) - 1ull));
-                        const uint32_t rb = a.row_ptr[x], deg = a.row_ptr[x + 1] - rb;
+                        const uint32_t rb = rb2[u], deg = re2[u] - rb;
                         if (!slot_has(xm, t)) {
                             // no state for t in x's row (cannot happen: a forwarder holds its
                             // topic, an origin gets the slot at publication): nothing is sent
                         } else if (deg <= 64 && x != s_org[k2[u]]) {
-                            msk2[u] = a.mmask[(int64_t)t * a.N + x];
+                            msk2[u] = mm2[u];
                             beg2[u] = rb;
                             len2[u] = (uint32_t)__popcll(msk2[u]);
                         } else if (a.hlist && x != s_org[k2[u]] &&
@@ -1220,11 +1286,17 @@ void k_send_tm(RoundArgs a_)
                     }
                     for (uint32_t it0 = w0; it0 < w1; it0 += kPerIt) {
                         const RoundArgs& a = kernarg0(a_);   // (re-read per iteration: SGPR pressure)
-                        uint32_t jv[P], fv[P], ev[P], iv[P], nv[P], kv[P];
+                        // a wave past the ragged end holds no copy (no block barrier in the iteration)
+                        if (it0 + (uint32_t)(wid * 64) >= w1) continue;
+                        // The iteration runs in phases over all P copies, each phase's memory
+                        // accesses issued back to back and waited for once: row state (A), the
+                        // committed bit (B), the cell (C), then counts and stores (D).  A lane
+                        // without a copy reads index 0 of each array and drops the result.
+                        uint32_t jv[P], fv[P], ev[P], iv[P], nv[P], kv[P], lpv[P];
                         int64_t pv[P];           // the sender's plane of topic t
                         uint8_t mfv[P], dsv[P], tfv[P];
-                        bool vv[P], mk[P];
-                        double xv[P];
+                        bool vv[P], mk[P], lsv[P], hbv[P];
+                        bool any_ls = false;
 #pragma unroll
                         for (int u = 0; u < P; ++u) {
                             const uint32_t fi = it0 + (uint32_t)(u * kTmThreads + tid);
@@ -1247,128 +1319,231 @@ void k_send_tm(RoundArgs a_)
                             const uint32_t k = fi - s_off[q];
                             const uint64_t msk = s_msk[q];
                             const uint32_t bq = s_beg[q];
-                            mk[u] = msk != 0 || (bq & kHubList);
-                            if (msk) ev[u] = bq + kth_bit(msk, k);
-                            else if (bq & kHubList) ev[u] = vv[u] ? a.hlist[(bq & ~kHubList) + k] : 0u;
-                            else if (a.sedge && vv[u]) ev[u] = a.sedge[bq + k];
-                            else ev[u] = s_beg[q] + k;
+                            const bool hub = (bq & kHubList) != 0;
+                            hbv[u] = hub;
+                            mk[u] = msk != 0 || hub;
+                            // a hub's listed edges, a shard's edges into owned peers: read below (A0)
+                            lsv[u] = vv[u] && !msk && (hub || a.sedge != nullptr);
+                            lpv[u] = (hub ? (bq & ~kHubList) : bq) + k;
+                            ev[u] = !vv[u] ? 0u : msk ? bq + kth_bit(msk, k) : bq + k;
+                            any_ls |= lsv[u];
+                        }
+                        // A0: the edges of list rows, one trip for all copies
+                        if (any_ls) {
+                            uint32_t le[P];
+#pragma unroll
+                            for (int u = 0; u < P; ++u) {
+                                le[u] = 0u;
+                                if (lsv[u]) le[u] = hbv[u] ? a.hlist[lpv[u]] : a.sedge[lpv[u]];
+                            }
+#pragma unroll
+                            for (int u = 0; u < P; ++u)
+                                if (lsv[u]) ev[u] = le[u];
                         }
                         uint32_t xq[PUSH ? P : 1];   // PUSH: the copy's bit (a cross edge), ~0: an owned receiver
                         uint64_t xbk[PUSH ? P : 1];  // ... a remote copy's xbits word (~0: none) and bit
                         uint64_t xbv[PUSH ? P : 1];
 #pragma unroll
                         for (int u = 0; u < P; ++u) {
-                            iv[u] = 0; mfv[u] = 0; dsv[u] = 0; tfv[u] = 0; nv[u] = 0; xv[u] = 0.0;
-                            if constexpr (PUSH) { xq[u] = ~0u; xbk[u] = ~0ull; xbv[u] = 0; }
-                            if (vv[u]) {
-                                const uint32_t e = ev[u];
-                                const uint8_t vd = s_vd[kv[u]];
-                                // a masked row's positions are its mesh (or direct) edges: the
-                                // router flags are read only for direct ones (below)
-                                const int64_t pe = pv[u] + e;
-                                iv[u] = a.col[e]; dsv[u] = a.dstate[e];
-                                if (!mk[u]) mfv[u] = a.mflags[pe];
-                                if constexpr (PUSH) {
-                                    xq[u] = a.xwq[e];
-                                } else {
-                                    tfv[u] = a.tflags[pe];
-                                    if (verdict_penalises(vd)) xv[u] = a.invalid[pe];
-                                    else if (vd == GSIM_VERDICT_ACCEPT) nv[u] = a.mcnt[pe];
-                                }
+                            // A: the row state of every copy (ev, pv are 0 for a lane without one).
+                            // A masked row's positions are its mesh (or direct) edges: the
+                            // router flags are read only for direct ones (below).  The invalid
+                            // counter of a penalised copy is read where it is raised (D).
+                            const uint32_t e = ev[u];
+                            const int64_t pe = pv[u] + e;
+                            mfv[u] = 0; tfv[u] = 0; nv[u] = 0;
+                            if constexpr (PUSH) { xbk[u] = ~0ull; xbv[u] = 0; }
+                            iv[u] = a.col[e]; dsv[u] = a.dstate[e];
+                            if (!mk[u]) mfv[u] = a.mflags[pe];
+                            if constexpr (PUSH) {
+                                xq[u] = a.xwq[e];
+                            } else {
+                                tfv[u] = a.tflags[pe];
+                                nv[u] = a.mcnt[pe];
                             }
                         }
+#pragma unroll
+                        for (int u = 0; u < P; ++u) {
+                            if (!vv[u]) { iv[u] = 0; dsv[u] = 0; mfv[u] = 0; tfv[u] = 0; nv[u] = 0; }
+                            if constexpr (PUSH) { if (!vv[u]) xq[u] = ~0u; }
+                        }
                         if constexpr (PUSH) {
-                            // the records of owned receivers only: a ghost's shard holds its own
+                            // the records of owned receivers only (a ghost's shard holds its own),
+                            // one trip for all copies
 #pragma unroll
                             for (int u = 0; u < P; ++u) {
-                                if (vv[u] && xq[u] == ~0u) {
-                                    const uint8_t vd = s_vd[kv[u]];
-                                    const int64_t pe = pv[u] + ev[u];
-                                    tfv[u] = a.tflags[pe];
-                                    if (verdict_penalises(vd)) xv[u] = a.invalid[pe];
-                                    else if (vd == GSIM_VERDICT_ACCEPT) nv[u] = a.mcnt[pe];
-                                }
+                                const bool own = vv[u] && xq[u] == ~0u;
+                                const int64_t pe = own ? pv[u] + ev[u] : 0;
+                                tfv[u] = a.tflags[pe];
+                                nv[u] = a.mcnt[pe];
                             }
+#pragma unroll
+                            for (int u = 0; u < P; ++u)
+                                if (!(vv[u] && xq[u] == ~0u)) { tfv[u] = 0; nv[u] = 0; }
                         }
                         int qpl[P];              // validation latency: queue plane of the copy (-1: none)
                         uint64_t qv[P];
                         uint32_t clw = 0;        // bit u: copy u claimed an unseen cell (its entry in s_cl)
 #pragma unroll
                         for (int u = 0; u < P; ++u) { qpl[u] = -1; qv[u] = 0; }
+                        // The rare paths' loads, behind their own tests and batched over the
+                        // copies (nothing is in flight when no lane takes them): the router
+                        // flags of a masked row's direct edges; the receiver's subscriptions
+                        // (flood publish, a direct peer, dynamic subscriptions); the publish
+                        // gate of a flooding origin's edge.
+                        uint8_t dmf[P];
+                        uint64_t sbv[P];
+                        bool fgate[P];
 #pragma unroll
                         for (int u = 0; u < P; ++u) {
-                            const uint32_t j = jv[u], e = ev[u], i = iv[u], k = kv[u];
-                            const uint32_t m = s_m[k], origin = s_org[k];
-                            const uint8_t vd = s_vd[k];
-                            const bool inv = vd != GSIM_VERDICT_ACCEPT;
-                            const bool pen = verdict_penalises(vd), seeable = vd != GSIM_VERDICT_SIGNATURE;
-                            const uint8_t ds = dsv[u], tf = tfv[u];
+                            const bool org = vv[u] && jv[u] == s_org[kv[u]];
+                            dmf[u] = 0; sbv[u] = 0; fgate[u] = true;
+                            if (vv[u] && mk[u] && (dsv[u] & GSIM_DS_DIRECT)) dmf[u] = a.mflags[pv[u] + ev[u]];
+                            if (vv[u] && ((a.flood && org) || (dsv[u] & GSIM_DS_DIRECT) || a.subdyn)) sbv[u] = a.sub[iv[u]];
+                        }
+                        if (a.flood) {
+                            uint32_t rv[P];
+                            uint8_t pg[P];
+                            double fs[P];
+#pragma unroll
+                            for (int u = 0; u < P; ++u) {
+                                const bool org = vv[u] && jv[u] == s_org[kv[u]];
+                                const bool far = a.sharded && (jv[u] < a.rlo || jv[u] >= a.rhi);
+                                rv[u] = 0; pg[u] = 0;
+                                if (org && far) pg[u] = a.pgate[ev[u]];
+                                if (org && !far) rv[u] = a.rev[ev[u]];
+                            }
+#pragma unroll
+                            for (int u = 0; u < P; ++u) {
+                                const bool org = vv[u] && jv[u] == s_org[kv[u]];
+                                const bool far = a.sharded && (jv[u] < a.rlo || jv[u] >= a.rhi);
+                                fs[u] = 0.0;
+                                if (org && !far) fs[u] = a.score[rv[u]];
+                            }
+#pragma unroll
+                            for (int u = 0; u < P; ++u) {
+                                const bool far = a.sharded && (jv[u] < a.rlo || jv[u] >= a.rhi);
+                                fgate[u] = far ? pg[u] != 0 : fs[u] >= a.pub_thr;
+                            }
+                        }
+                        // the copies that reach their receiver
+                        bool tgv[P], okv[P];
+#pragma unroll
+                        for (int u = 0; u < P; ++u) {
+                            const uint32_t j = jv[u], i = iv[u], k = kv[u];
+                            const uint32_t origin = s_org[k];
+                            const uint8_t ds = dsv[u];
+                            const bool sub_i = (sbv[u] >> t) & 1ull;
                             bool sel;
-                            if (mk[u]) sel = !(ds & GSIM_DS_DIRECT) || (a.mflags[pv[u] + e] & GSIM_TF_MESH);
+                            if (mk[u]) sel = !(ds & GSIM_DS_DIRECT) || (dmf[u] & GSIM_TF_MESH);
                             else sel = (mfv[u] & (j == origin ? s_ow[k] : GSIM_TF_MESH)) != 0;
-                            if (a.flood && vv[u] && j == origin)
-                                sel = ((a.sub[i] >> t) & 1ull) &&
-                                      ((a.sharded && (j < a.rlo || j >= a.rhi)) ? a.pgate[e] != 0
-                                                                                : a.score[a.rev[e]] >= a.pub_thr);
-                            if (vv[u] && (ds & GSIM_DS_DIRECT) && !sel) sel = (a.sub[i] >> t) & 1ull;
+                            if (a.flood && vv[u] && j == origin) sel = sub_i && fgate[u];
+                            if (vv[u] && (ds & GSIM_DS_DIRECT) && !sel) sel = sub_i;
                             const bool tg = vv[u] && sel && (ds & GSIM_DS_CONNECTED) && i != fv[u] && i != origin;
                             const bool remote = i < a.rlo || i >= a.rhi;
-                            if (tg && a.tr.ev) {         // the copy's RPC: SendRPC / RecvRPC (trace.go:250-297)
-                                const int64_t ts = round_time(a, a.g);
-                                const uint64_t tm = ((uint64_t)a.g << 32) | m;
-                                if (a.tr.on(j)) a.tr.push(ts, tm, j, i, t, GSIM_TRACE_SEND_RPC, 0);
-                                // (a pushed copy's RecvRPC: only the sender's shard knows of it)
-                                if (a.tr.on_any(i)) a.tr.push(ts, tm, i, j, t, GSIM_TRACE_RECV_RPC, 0);
-                            }
+                            tgv[u] = tg;
+                            okv[u] = false;
                             if constexpr (PUSH) {
                                 // the receiver's shard delivers it (its AcceptFrom, records, cell):
                                 // its bit, set below for the whole wave (xbits_or_wave)
                                 if (tg && remote) {
                                     const uint32_t xb = xq[u];
-                                    xbk[u] = (uint64_t)((int64_t)m * a.xbw + (xb >> 6));
+                                    xbk[u] = (uint64_t)((int64_t)s_m[k] * a.xbw + (xb >> 6));
                                     xbv[u] = 1ull << (xb & 63u);
                                     continue;
                                 }
                             }
                             const bool ok = tg && !remote && (ds & GSIM_DS_ACCEPT);
                             n_gray += tg && !remote && !ok;
-                            if (!ok) continue;
-                            if constexpr (GT) {                  // the peer gater (gater_accept)
-                                if (!gater_accept(a, i, e, m, j)) continue;
-                            }
+                            okv[u] = ok;
+                        }
+                        if constexpr (GT) {                      // the peer gater (gater_accept)
+#pragma unroll
+                            for (int u = 0; u < P; ++u)
+                                if (okv[u] && !gater_accept(a, iv[u], ev[u], s_m[kv[u]], jv[u])) okv[u] = false;
+                        }
+#pragma unroll
+                        for (int u = 0; u < P; ++u) {
                             // a topic the receiver left: skipped (pubsub.go:1094-1098)
-                            if (a.subdyn && !((a.sub[i] >> t) & 1ull)) continue;
-                            if constexpr (GT) gater_copy(a, e, !seeable);
-                            n_acc++;
-                            if (a.tr.on(i))
-                                a.tr.push(round_time(a, a.g), ((uint64_t)a.g << 32) | m, i, j, t,
-                                          seeable ? kTraceCopy : (uint8_t)GSIM_TRACE_REJECT_MESSAGE, vd);
+                            if (a.subdyn && !((sbv[u] >> t) & 1ull)) okv[u] = false;
+                            n_acc += okv[u];
+                        }
+                        // B: the committed bits of every copy that passed (else the first word of
+                        // the slot's range, dropped)
+                        uint64_t bwv[P];
+#pragma unroll
+                        for (int u = 0; u < P; ++u)
+                            bwv[u] = a.seenbm[(int64_t)s_m[kv[u]] * a.nw + (okv[u] ? (int64_t)(iv[u] >> 6) : wlo)];
+                        bool sbt[P], knv[P], fdv[P], acv[P];
+                        int64_t civ[P];
+                        uint64_t cvv[P], ccv[P];
+#pragma unroll
+                        for (int u = 0; u < P; ++u) {
+                            const uint32_t i = iv[u], k = kv[u];
+                            const uint8_t vd = s_vd[k];
+                            const bool inv = vd != GSIM_VERDICT_ACCEPT;
+                            const bool pen = verdict_penalises(vd);
+                            const uint8_t ds = dsv[u], tf = tfv[u];
                             const bool sc = scored_t && (ds & GSIM_DS_TRACKED);
                             const uint32_t L = LAT ? s_lat[k] : 0u;
-                            const uint64_t* s_bm = a.seenbm + (int64_t)m * a.nw + wlo;
-                            const int64_t bw = ((int64_t)i >> 6) - wlo;
                             // a committed cell need not be read when the copy cannot be
                             // credited; with a validation latency the credit is decided at
                             // completion (mesh and record then), so only an unscored topic
                             // or an ignored / throttled message skips it
-                            const bool sbit = (s_bm[bw] >> (i & 63)) & 1ull;   // committed before this round
-                            const bool known = sbit && (L ? (!scored_t || (inv && !pen))
-                                                          : (s_wa[k] || !sc || inv || !(tf & GSIM_TF_IN_MESH)));
-                            // the receiver's cell (a member of t: mesh, direct, fanout and flood
-                            // targets all hold the topic, §2); -1 cannot happen
-                            const int64_t ci = known ? 0 : SP ? a.cs.at((int64_t)s_cb[k], t, i) : (int64_t)m * a.cs.n + i;
-                            if (SP && ci < 0) continue;
-                            uint32_t lo_w = j;
+                            const bool sbit = (bwv[u] >> (i & 63)) & 1ull;   // committed before this round
+                            sbt[u] = sbit;
+                            knv[u] = sbit && (L ? (!scored_t || (inv && !pen))
+                                                : (s_wa[k] || !sc || inv || !(tf & GSIM_TF_IN_MESH)));
+                            acv[u] = okv[u];
+                            civ[u] = (int64_t)s_m[k] * a.cs.n + i;
+                            uint32_t lo_w = jv[u];
                             if (sc && !inv) {
                                 lo_w |= kCreditFirst;
                                 if (window < 0 && (tf & GSIM_TF_IN_MESH)) lo_w |= kCreditMesh;
                             }
-                            const uint64_t cv = ((uint64_t)(claim_hi | e) << 32) | lo_w;
-                            // a receiver that had not seen m before this round (no claims of
-                            // round g-1 remain without a latency): the claim is the cell's only
-                            // access -- atomicMin keeps a lower edge's claim of this round and
-                            // returns what the cell held (a load, then the claim, otherwise)
-                            const bool fold = !LAT && !sbit && seeable;
+                            cvv[u] = ((uint64_t)(claim_hi | ev[u]) << 32) | lo_w;
+                        }
+                        // the receiver's cell (a member of t: mesh, direct, fanout and flood
+                        // targets all hold the topic, §2); -1 cannot happen
+                        if constexpr (SP) {
+                            // member-compacted cells: the table words of every copy whose cell
+                            // is read, one trip
+                            const bool spt = (a.cs.sparse >> t) & 1ull;
+                            uint64_t tb[P];
+                            uint32_t tpre[P];
+#pragma unroll
+                            for (int u = 0; u < P; ++u) {
+                                const bool need = spt && acv[u] && !knv[u];
+                                const int64_t wi_ = (int64_t)t * a.cs.nw + (need ? (int64_t)(iv[u] >> 6) : 0);
+                                tb[u] = ~0ull;
+                                tpre[u] = (iv[u] >> 6) * 64u;
+                                if (spt) { tb[u] = a.cs.mbits[wi_]; tpre[u] = a.cs.mpre[wi_]; }
+                            }
+#pragma unroll
+                            for (int u = 0; u < P; ++u) {
+                                loads_done(tb[u], tpre[u]);
+                                if (!(spt && acv[u] && !knv[u])) { tb[u] = ~0ull; tpre[u] = (iv[u] >> 6) * 64u; }
+                            }
+#pragma unroll
+                            for (int u = 0; u < P; ++u) {
+                                const uint64_t bit = 1ull << (iv[u] & 63);
+                                civ[u] = (tb[u] & bit) ? (int64_t)s_cb[kv[u]] + tpre[u] + __popcll(tb[u] & (bit - 1)) : -1;
+                                if (civ[u] < 0 && !knv[u]) acv[u] = false;
+                            }
+                        }
+                        // C: the cell of every copy -- a receiver that had not seen m before
+                        // this round (no claims of round g-1 remain without a latency): the
+                        // claim is the cell's only access -- atomicMin keeps a lower edge's
+                        // claim of this round and returns what the cell held (a load, then the
+                        // claim, otherwise)
+#pragma unroll
+                        for (int u = 0; u < P; ++u) {
+                            const bool seeable = s_vd[kv[u]] != GSIM_VERDICT_SIGNATURE;
+                            const bool known = knv[u], fold = acv[u] && !LAT && !sbt[u] && seeable;
+                            const int64_t ci = civ[u];
+                            const uint64_t cv = cvv[u];
+                            fdv[u] = fold;
+                            if (!acv[u]) { ccv[u] = 0ull; continue; }
 #if defined(GSIM_DIAG_CLAIM)
                             // timing diagnostic (wrong first-delivery totals; 2: racy winners)
                             uint64_t c;
@@ -1387,26 +1562,62 @@ void k_send_tm(RoundArgs a_)
                                                                              __HIP_MEMORY_SCOPE_AGENT)
                                                     : a.cs.cell[ci];
 #endif
+                            ccv[u] = c;
+                        }
+                        // the round validation completed (or completes) in; -1: unclaimed or
+                        // claimed in this round
+                        int64_t srv[P];
+                        bool c2v[P];             // a cell that was loaded: the claim follows
+                        bool inw[P];
+#pragma unroll
+                        for (int u = 0; u < P; ++u) {
+                            const uint32_t k = kv[u];
+                            const bool seeable = s_vd[k] != GSIM_VERDICT_SIGNATURE;
+                            const uint32_t L = LAT ? s_lat[k] : 0u;
+                            const uint64_t c = ccv[u];
                             const uint32_t chi = (uint32_t)(c >> 32);
-                            // the round validation completed (or completes) in; -1: unclaimed
-                            // or claimed in this round
                             int64_t seen_round = -1;
-                            if (known) seen_round = a.g - 1;
+                            if (knv[u]) seen_round = a.g - 1;
                             else if (c != kUnseen64) {
                                 if (!(chi & kClaim)) seen_round = chi;
                                 else if (((chi >> 30) & 1u) != par) seen_round = a.g - 1 + L;
                             }
-                            if (fold || (seeable && seen_round < 0 && (c == kUnseen64 || (chi & kEdgeMask) > e))) {
-                                const uint64_t prev = fold ? c
-                                                           : __hip_atomic_fetch_min(a.cs.cell + ci, cv, __ATOMIC_RELAXED,
-                                                                                    __HIP_MEMORY_SCOPE_AGENT);
-                                if (prev == kUnseen64) {
-                                    n_first++;
-                                    clm |= 1ull << k;
-                                    if constexpr (SP && !LAT) {
-                                        clw |= 1u << u;
-                                        s_cl[u * kTmThreads + tid] = cl_entry(a, i, m, ci, (int64_t)s_cb[k]);
-                                    }
+                            srv[u] = seen_round;
+                            c2v[u] = acv[u] && !fdv[u] && seeable && seen_round < 0 &&
+                                     (c == kUnseen64 || (chi & kEdgeMask) > ev[u]);
+                            // the duplicate's credit window (the round table's read: before the stores)
+                            inw[u] = knv[u] ? true
+                                   : seen_round >= 0 ? (acv[u] && a.now - round_time(a, seen_round) <= window)
+                                                     : (window >= 0);
+                        }
+                        // ... for all copies together, after the one wait on the cells
+                        uint64_t prv[P];
+#pragma unroll
+                        for (int u = 0; u < P; ++u) {
+                            prv[u] = fdv[u] ? ccv[u] : 0ull;
+                            if (c2v[u])
+                                prv[u] = __hip_atomic_fetch_min(a.cs.cell + civ[u], cvv[u], __ATOMIC_RELAXED,
+                                                                __HIP_MEMORY_SCOPE_AGENT);
+                        }
+                        // D: counts, the claim-list entry, the records' stores, the latency queue
+#pragma unroll
+                        for (int u = 0; u < P; ++u) {
+                            if (!acv[u]) continue;
+                            const uint32_t e = ev[u], i = iv[u], k = kv[u];
+                            const uint32_t m = s_m[k];
+                            const uint8_t vd = s_vd[k];
+                            const bool inv = vd != GSIM_VERDICT_ACCEPT;
+                            const bool pen = verdict_penalises(vd), seeable = vd != GSIM_VERDICT_SIGNATURE;
+                            const uint8_t ds = dsv[u], tf = tfv[u];
+                            const bool sc = scored_t && (ds & GSIM_DS_TRACKED);
+                            const uint32_t L = LAT ? s_lat[k] : 0u;
+                            const int64_t seen_round = srv[u];
+                            if ((fdv[u] || c2v[u]) && prv[u] == kUnseen64) {
+                                n_first++;
+                                clm |= 1ull << k;
+                                if constexpr (SP && !LAT) {
+                                    clw |= 1u << u;
+                                    s_cl[u * kTmThreads + tid] = cl_entry(a, i, m, civ[u], (int64_t)s_cb[k]);
                                 }
                             }
                             if (L && seeable && (seen_round < 0 || seen_round > a.g)) {
@@ -1431,13 +1642,10 @@ void k_send_tm(RoundArgs a_)
                             if (!sc) continue;
                             const int64_t ir = pv[u] + e;
                             if (pen) {
-                                a.invalid[ir] = xv[u] + 1.0;
+                                a.invalid[ir] = a.invalid[ir] + 1.0;     // (this block's record alone)
                                 inv_mark(a);
                             } else if (!inv && (tf & GSIM_TF_IN_MESH)) {
-                                const bool in_window = known ? true
-                                                     : seen_round >= 0 ? (a.now - round_time(a, seen_round) <= window)
-                                                                       : (window >= 0);
-                                if (in_window) {
+                                if (inw[u]) {
                                     uint32_t n = nv[u];
                                     if (n == 255u) {
                                         a.meshd[ir] = apply_incs(a.meshd[ir], n, mcap);
@@ -1445,6 +1653,28 @@ void k_send_tm(RoundArgs a_)
                                     }
                                     a.mcnt[ir] = (uint8_t)(n + 1);
                                 }
+                            }
+                        }
+                        if constexpr (GT) {
+#pragma unroll
+                            for (int u = 0; u < P; ++u)
+                                if (okv[u]) gater_copy(a, ev[u], s_vd[kv[u]] == GSIM_VERDICT_SIGNATURE);
+                        }
+                        if (a.tr.ev) {
+                            // the copy's RPC: SendRPC / RecvRPC (trace.go:250-297), and the copy
+                            // itself at a traced receiver
+                            const int64_t ts = round_time(a, a.g);
+#pragma unroll
+                            for (int u = 0; u < P; ++u) {
+                                const uint32_t j = jv[u], i = iv[u];
+                                const uint8_t vd = s_vd[kv[u]];
+                                const uint64_t tm = ((uint64_t)a.g << 32) | s_m[kv[u]];
+                                if (tgv[u] && a.tr.on(j)) a.tr.push(ts, tm, j, i, t, GSIM_TRACE_SEND_RPC, 0);
+                                // (a pushed copy's RecvRPC: only the sender's shard knows of it)
+                                if (tgv[u] && a.tr.on_any(i)) a.tr.push(ts, tm, i, j, t, GSIM_TRACE_RECV_RPC, 0);
+                                if (okv[u] && a.tr.on(i))
+                                    a.tr.push(ts, tm, i, j, t,
+                                              vd != GSIM_VERDICT_SIGNATURE ? kTraceCopy : (uint8_t)GSIM_TRACE_REJECT_MESSAGE, vd);
                             }
                         }
                         if constexpr (PUSH) {
