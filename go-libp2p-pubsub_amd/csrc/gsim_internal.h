@@ -181,6 +181,18 @@ __device__ __forceinline__ int64_t slot_idx(uint64_t m, int32_t t, int64_t E, in
 {
     return (int64_t)__popcll(m & ((1ull << t) - 1ull)) * E + x;
 }
+// ... in a kernel instance compiled for one layout: Dense instances run only
+// where there are no slot masks (every mask is ~0), so topic t is plane t
+template <bool Dense>
+__device__ __forceinline__ bool slot_has_of(uint64_t m, int32_t t)
+{
+    if constexpr (Dense) return true; else return slot_has(m, t);
+}
+template <bool Dense>
+__device__ __forceinline__ int64_t slot_idx_of(uint64_t m, int32_t t, int64_t E, int64_t x)
+{
+    if constexpr (Dense) return (int64_t)t * E + x; else return slot_idx(m, t, E, x);
+}
 // topic of the p-th plane of a row owner with mask m (p < popcount(m))
 __device__ __forceinline__ int32_t slot_topic(uint64_t m, int32_t p)
 {

@@ -11,6 +11,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <type_traits>
 #include <vector>
 
 #include "gsim.h"
@@ -246,6 +247,43 @@ __device__ __forceinline__ uint32_t group_min_u32(uint32_t v, int grp)
     }
 }
 
+// The bits of a wave ballot that belong to the W-lane group `grp`, moved down
+// to bit 0: bit q is the group's row position q.  A group of at most 32 lanes
+// lies in one half of the ballot, so its counts, tests and first/last set bit
+// are single-dword operations on a value picked from two SGPRs; W = 64 keeps
+// the whole (scalar) ballot.
+template <int W>
+struct GroupBits {
+    static_assert(W == 64 || W == 32 || W == 16 || W == 8, "groups of 8, 16, 32 or 64 lanes");
+    using bits_t = std::conditional_t<W == 64, uint64_t, uint32_t>;
+    int grp;
+    __device__ explicit GroupBits(int grp_) : grp(grp_) {}
+    __device__ bits_t of(uint64_t bal) const
+    {
+        if constexpr (W == 64) {
+            return bal;
+        } else {
+            constexpr int H = 32 / W;           // groups per dword
+            const uint32_t half = grp >= H ? (uint32_t)(bal >> 32) : (uint32_t)bal;
+            if constexpr (W == 32) return half;
+            else return (half >> ((grp & (H - 1)) * W)) & ((1u << W) - 1u);
+        }
+    }
+    __device__ static int popc(bits_t x)
+    {
+        if constexpr (W == 64) return __popcll(x); else return __popc(x);
+    }
+    // the lowest / highest position set (x != 0)
+    __device__ static int lowest(bits_t x)
+    {
+        if constexpr (W == 64) return __ffsll((long long)x) - 1; else return __ffs((int)x) - 1;
+    }
+    __device__ static int highest(bits_t x)
+    {
+        if constexpr (W == 64) return 63 - __clzll((long long)x); else return 31 - __clz((int)x);
+    }
+};
+
 // The global id of a local peer: selection keys are those of the whole network.
 __device__ __forceinline__ uint32_t glob(const HbArgs& a, uint32_t p) { return a.gid ? a.gid[p] : p; }
 
@@ -273,40 +311,58 @@ __device__ __forceinline__ uint32_t hb_key_hi(const HbArgs& a, uint32_t obs, int
 // reductions.  Keys below tau precede every key above it whatever the lane, so
 // the result is exactly the `count` smallest (key, lane) pairs.
 //
-// W-lane groups (W = 32: two observers per wave): every ballot is masked to
-// the caller's group `gm`, the lane index keeps breaking ties (the group's
-// lanes are in row order), and a group may run this alone.
+// W-lane groups (W = 32: two observers per wave): every ballot is taken as
+// the bits of the caller's group `grp` (GroupBits: bit q is row position q, one
+// dword for a group of at most 32 lanes), the row position keeps breaking
+// ties (the group's lanes are in row order), and a group may run this alone.
+#if GSIM_DIAG_HB == 2
+// Diagnostic build -DGSIM_DIAG_HB=2 (counts only, results unchanged; gsim_diag_hb_counts
+// returns these instead): [0] lane-group selections that reach the adjust loops, [1] their
+// drop and [2] their add iterations, [3] wave-topics that take the maintenance branch
+__device__ unsigned long long g_hb_sel[4];
+#endif
+
 template <int W = 64>
 __device__ bool select_smallest(const HbArgs& a, bool cand, int count, uint32_t obs, int32_t t, uint32_t purpose,
-                                uint32_t col, uint32_t pos, uint64_t gm = ~0ull, int grp = 0)
+                                uint32_t col, uint32_t pos, int grp = 0)
 {
-    const uint64_t avail = __ballot(cand) & gm;
-    const int n = __popcll(avail);
+    using GB = GroupBits<W>;
+    const GB gb(grp);
+    const int n = GB::popc(gb.of(__ballot(cand)));
     if (n == 0) return false;
     if (count <= 0 || n <= count) return cand;
-    const int lane = threadIdx.x & 63;
+    const int gl = (int)(threadIdx.x & (W - 1));
     uint32_t hi = 0xFFFFFFFFu;
     if (cand) hi = hb_key_hi(a, obs, t, purpose, col, pos);
     // any threshold gives the same selection; it only sets how many lanes the
-    // loops below adjust (fp32: no 64-bit integer division)
-    const uint32_t tau = (uint32_t)((float)count / (float)n * 4294967040.0f);
+    // loops below adjust (fp32 reciprocal: no division, the estimate's last
+    // bit is of no account)
+    const uint32_t tau = (uint32_t)((float)count * __builtin_amdgcn_rcpf((float)n) * 4294967040.0f);
     bool sel = cand && hi < tau;
-    int c = __popcll(__ballot(sel) & gm);
-    while (c > count) {                 // drop the largest (key, lane) among the selected
+    int c = GB::popc(gb.of(__ballot(sel)));
+#if GSIM_DIAG_HB == 2
+    if (gl == 0) atomicAdd(&g_hb_sel[0], 1ull);
+#endif
+    while (c > count) {                 // drop the largest (key, position) among the selected
         const uint32_t mx = ~group_min_u32<W>(sel ? ~hi : 0xFFFFFFFFu, grp);
-        const uint64_t at = __ballot(sel && hi == mx) & gm;
-        const int win = 63 - __clzll((long long)at);
-        if (lane == win) sel = false;
+        const int win = GB::highest(gb.of(__ballot(sel && hi == mx)));
+        if (gl == win) sel = false;
         --c;
+#if GSIM_DIAG_HB == 2
+        if (gl == 0) atomicAdd(&g_hb_sel[1], 1ull);
+#endif
     }
     uint32_t rest = (cand && !sel) ? hi : 0xFFFFFFFFu;
-    uint64_t left = __ballot(cand && !sel) & gm;
-    while (c < count) {                 // add the smallest (key, lane) among the others
+    typename GB::bits_t left = gb.of(__ballot(cand && !sel));
+    while (c < count) {                 // add the smallest (key, position) among the others
         const uint32_t mn = group_min_u32<W>(rest, grp);
-        const int win = __ffsll((long long)(__ballot(rest == mn) & left)) - 1;
-        left &= ~(1ull << win);
-        if (lane == win) { sel = true; rest = 0xFFFFFFFFu; }
+        const int win = GB::lowest(gb.of(__ballot(rest == mn)) & left);
+        left &= ~((typename GB::bits_t)1 << win);
+        if (gl == win) { sel = true; rest = 0xFFFFFFFFu; }
         ++c;
+#if GSIM_DIAG_HB == 2
+        if (gl == 0) atomicAdd(&g_hb_sel[2], 1ull);
+#endif
     }
     return sel;
 }
@@ -321,6 +377,12 @@ __device__ __forceinline__ const HbArgs& hb_launder(const HbArgs& a)
 {
     return kernarg0(a);        // (the same re-read; debug builds check its argument)
 }
+// ... again where Again holds, else the earlier re-read `cur`
+template <bool Again>
+__device__ __forceinline__ const HbArgs& hb_launder_if(const HbArgs& a, const HbArgs& cur)
+{
+    if constexpr (Again) return hb_launder(a); else return cur;
+}
 
 // The score bits of one (observer, neighbour, topic) record, loaded on first
 // use: Graft/Prune are rare, and the record lives at rev[e] (record order,
@@ -330,10 +392,11 @@ struct ScoreFlags {
     bool ok = false;     // the neighbour holds a slot for t (else the record is absent: zero)
     uint8_t v = 0, v0 = 0;
     bool have = false;
+    template <bool Dense = false>
     __device__ void at(uint64_t mj, int32_t t, int64_t E, uint32_t rv)
     {
-        ok = slot_has(mj, t);
-        ir = slot_idx(mj, t, E, rv);
+        ok = slot_has_of<Dense>(mj, t);
+        ir = slot_idx_of<Dense>(mj, t, E, rv);
     }
     __device__ uint8_t& get(const HbArgs& a)
     {
@@ -465,13 +528,17 @@ __device__ double score_of_record(const HbArgs& a_, uint32_t rv, uint32_t col)
 // smaller, else the target smallest keys.  A lane is selected if any of its
 // instances is.  Must be called by the whole wave.
 template <int W = 64>
-__device__ bool gossip_targets(const HbArgs& a, bool cand, bool tpeer, uint32_t obs, int32_t t, uint32_t col,
-                               uint32_t pos, uint64_t gm = ~0ull, int grp = 0)
+__device__ __forceinline__ bool gossip_targets(const HbArgs& a, bool cand, bool tpeer, uint32_t obs, int32_t t, uint32_t col,
+                               uint32_t pos, int grp = 0)
 {
-    const int c = __popcll(__ballot(cand) & gm);
+    using GB = GroupBits<W>;
+    using bits_t = typename GB::bits_t;
+    const GB gb(grp);
+    const int c = GB::popc(gb.of(__ballot(cand)));
     bool dup = false;
-    if (c < a.Dlo) dup = select_smallest<W>(a, tpeer, a.Dlo - c, obs, t, P_GOSSIP_FILL, col, pos, gm, grp);
-    const int n = c + __popcll(__ballot(dup) & gm);
+    if (c < a.Dlo) dup = select_smallest<W>(a, tpeer, a.Dlo - c, obs, t, P_GOSSIP_FILL, col, pos, grp);
+    bits_t av2 = gb.of(__ballot(dup));
+    const int n = c + GB::popc(av2);
     if (n == 0) return false;
     int target = a.dlazy;
     const int factor = (int)(a.gossip_factor * (double)n);
@@ -479,23 +546,23 @@ __device__ bool gossip_targets(const HbArgs& a, bool cand, bool tpeer, uint32_t 
     if (target >= n) return cand || dup;
     // each lane holds up to two instances (candidate, fill duplicate)
     // no fill duplicates (the usual case): one instance per lane
-    if (!(__ballot(dup) & gm)) return select_smallest<W>(a, cand, target, obs, t, P_GOSSIP, col, pos, gm, grp);
+    if (!av2) return select_smallest<W>(a, cand, target, obs, t, P_GOSSIP, col, pos, grp);
     uint32_t h1 = cand ? hb_key_hi(a, obs, t, P_GOSSIP, col, pos) : 0xFFFFFFFFu;
     uint32_t h2 = dup ? hb_key_hi(a, obs, t, P_GOSSIP_DUP, col, pos) : 0xFFFFFFFFu;
-    uint64_t av1 = __ballot(cand) & gm, av2 = __ballot(dup) & gm;
-    const int lane = threadIdx.x & 63;
+    bits_t av1 = gb.of(__ballot(cand));
+    const int gl = (int)(threadIdx.x & (W - 1));
     bool sel = false;
     for (int q = 0; q < target; ++q) {
         // a lane's next instance: its smaller key (instance 1 on a tie)
-        const bool has1 = (av1 >> lane) & 1ull, has2 = (av2 >> lane) & 1ull;
+        const bool has1 = (av1 >> gl) & 1, has2 = (av2 >> gl) & 1;
         const bool use1 = has1 && (!has2 || h1 <= h2);
         const uint32_t mine = use1 ? h1 : (has2 ? h2 : 0xFFFFFFFFu);
         const uint32_t mn = group_min_u32<W>(mine, grp);
         const bool at_min = mine == mn && (has1 || has2);
-        const int win = __ffsll((long long)(__ballot(at_min) & gm)) - 1;
+        const int win = GB::lowest(gb.of(__ballot(at_min)));
         // which instance the winner used, from a ballot (no lane shuffle)
-        if ((__ballot(at_min && use1) >> win) & 1ull) av1 &= ~(1ull << win); else av2 &= ~(1ull << win);
-        if (lane == win) sel = true;
+        if ((gb.of(__ballot(at_min && use1)) >> win) & 1) av1 &= ~((bits_t)1 << win); else av2 &= ~((bits_t)1 << win);
+        if (gl == win) sel = true;
     }
     return sel;
 }
@@ -515,13 +582,17 @@ __device__ bool gossip_targets(const HbArgs& a, bool cand, bool tpeer, uint32_t 
 // thread holds positions pos(0) .. pos(V-1), and every per-position value
 // crosses the interface as an array of V.
 
-template <int W>
+// Dense: every peer holds a slot for every topic (no slot masks), so a topic's
+// plane is its number (Slots below).
+template <int W, bool Dense_ = false>
 struct WaveGroup {
     static constexpr int V = 1;
+    static constexpr bool kDense = Dense_;
     static constexpr int LP = 64 / W;     // topics per lane of the mcache-put cache
     int lane, grp, gl, base;
     uint64_t gm;
     int32_t lpv[LP];
+    bool opp_tick = false;                // an opportunistic-grafting heartbeat (k_heartbeat sets it)
     __device__ explicit WaveGroup(int lane_)
         : lane(lane_), grp(lane_ / W), gl(lane_ % W), base((lane_ / W) * W),
           gm(W == 64 ? ~0ull : (((1ull << W) - 1) << ((lane_ / W) * W)))
@@ -529,17 +600,45 @@ struct WaveGroup {
     }
     __device__ int pos(int = 0) const { return gl; }
     __device__ int span() const { return W; }
-    __device__ int count(const bool* p) const { return __popcll(__ballot(p[0]) & gm); }
-    __device__ bool any(const bool* p) const { return (__ballot(p[0]) & gm) != 0; }
+    // the group's bits of a ballot, bit q = row position q
+    __device__ typename GroupBits<W>::bits_t bits(bool p) const { return GroupBits<W>(grp).of(__ballot(p)); }
+    __device__ int count(const bool* p) const { return GroupBits<W>::popc(bits(p[0])); }
+    __device__ bool any(const bool* p) const { return bits(p[0]) != 0; }
+    // The steady-state test of a topic's mesh maintenance (hb_observer), for
+    // every group of the wave at once: no group running this has a mesh size
+    // (positions with m) outside [Dlo, Dhi], fewer than Dout outbound mesh
+    // peers (mo) or a mesh peer of negative score (neg).  Wave-uniform.
+    static constexpr bool kSteadyTest = true;
+    __device__ bool steady(bool m, bool mo, bool neg, int Dlo, int Dhi, int Dout) const
+    {
+        if (__ballot(neg)) return false;
+        if constexpr (W >= 32) {
+            // whole dwords of the ballots: the counts of both groups are scalar
+            const uint64_t bm = __ballot(m), bo = __ballot(mo), ex = __ballot(true);
+            bool ok = true;
+#pragma unroll
+            for (int h = 0; h < 64 / W; ++h) {
+                constexpr uint64_t gmask = W == 64 ? ~0ull : 0xFFFFFFFFull;
+                const int sh = W == 64 ? 0 : h * W;
+                if (!((ex >> sh) & gmask)) continue;        // this group sits the topic out
+                const int l = __popcll((bm >> sh) & gmask), ob = __popcll((bo >> sh) & gmask);
+                ok = ok && l >= Dlo && l <= Dhi && ob >= Dout;
+            }
+            return ok;
+        } else {
+            const int l = GroupBits<W>::popc(bits(m)), ob = GroupBits<W>::popc(bits(mo));
+            return !__ballot(l < Dlo || l > Dhi || ob < Dout);
+        }
+    }
     __device__ void select(const HbArgs& a, const bool* cand, int count, uint32_t obs, int32_t t, uint32_t purpose,
                            const uint32_t* col, bool* out)
     {
-        out[0] = select_smallest<W>(a, cand[0], count, obs, t, purpose, col[0], (uint32_t)gl, gm, grp);
+        out[0] = select_smallest<W>(a, cand[0], count, obs, t, purpose, col[0], (uint32_t)gl, grp);
     }
     __device__ void gossip(const HbArgs& a, const bool* cand, const bool* tpeer, uint32_t obs, int32_t t,
                            const uint32_t* col, bool* out)
     {
-        out[0] = gossip_targets<W>(a, cand[0], tpeer[0], obs, t, col[0], (uint32_t)gl, gm, grp);
+        out[0] = gossip_targets<W>(a, cand[0], tpeer[0], obs, t, col[0], (uint32_t)gl, grp);
     }
     // a lane's value at position q of the group (every lane asks for the same q)
     template <typename T>
@@ -561,7 +660,7 @@ struct WaveGroup {
     // the value at the lowest position where p holds (p must hold somewhere)
     __device__ double at_lowest(const bool* p, const double* v) const
     {
-        return __shfl(v[0], (int)__ffsll((long long)(__ballot(p[0]) & gm)) - 1, 64);
+        return __shfl(v[0], base + GroupBits<W>::lowest(bits(p[0])), 64);
     }
     // newest mcache put of topic t by observer obs (GetGossipIDs non-empty test):
     // group lane gl caches topics gl, gl + W, ... (T <= 64)
@@ -569,7 +668,7 @@ struct WaveGroup {
     __device__ uint64_t topic_mask(bool p) const { return __ballot(p) & gm; }
     // bit q = p at the group's row position q (the delivery's mesh masks)
     static constexpr bool kRowMask = true;
-    __device__ uint64_t row_mask(const bool* p) const { return (__ballot(p[0]) & gm) >> base; }
+    __device__ uint64_t row_mask(const bool* p) const { return bits(p[0]); }
     __device__ void load_lastput(const HbArgs& a, int64_t obs, uint64_t subi, bool ovalid)
     {
 #pragma unroll
@@ -591,6 +690,9 @@ struct WaveGroup {
 template <int B, int VV = 1>
 struct BlockGroup {
     static constexpr int V = VV;
+    static constexpr bool kDense = false;       // the hub classes keep the slot-mask index
+    static constexpr bool kSteadyTest = false;  // ... and run the maintenance of every topic
+    static constexpr bool opp_tick = false;     // (WaveGroup's flag: not held here)
     static constexpr int NW = B / 64;
     static constexpr int P = B * V;       // positions
     struct Shared {
@@ -810,6 +912,7 @@ __device__ __forceinline__ void hb_observer(const HbArgs& a_, Grp& g, int64_t ob
 {
         const HbArgs& a = a_;
         constexpr int V = Grp::V;
+        constexpr bool kDense = Grp::kDense;   // (then a.smask is null: mi and every mj are ~0)
         const uint32_t b = ovalid ? a.row_ptr[obs] : 0u;
         const int deg = ovalid ? (int)(a.row_ptr[obs + 1] - b) : 0;
         const uint32_t gobs = ovalid ? glob(a, (uint32_t)obs) : 0u;
@@ -863,8 +966,8 @@ __device__ __forceinline__ void hb_observer(const HbArgs& a_, Grp& g, int64_t ob
             for (int v = 0; v < V; ++v) {
                 if (!valid[v]) continue;
                 for (int32_t t = 0; t < a.T; ++t) {
-                    if (!slot_has(mi, t)) continue;
-                    const int64_t i = slot_idx(mi, t, a.E, e[v]);
+                    if (!slot_has_of<kDense>(mi, t)) continue;
+                    const int64_t i = slot_idx_of<kDense>(mi, t, a.E, e[v]);
                     const int64_t bo = a.backoff[i];
                     if (bo != 0 && bo + kBackoffSlack < a.now) a.backoff[i] = 0;
                 }
@@ -883,35 +986,73 @@ __device__ __forceinline__ void hb_observer(const HbArgs& a_, Grp& g, int64_t ob
               const int32_t t = t0 + j;
 #pragma unroll
               for (int v = 0; v < V; ++v)
-                  flc[j][v] = (t < a.T && valid[v] && ((subi >> t) & 1ull)) ? a.mflags[slot_idx(mi, t, a.E, e[v])] : 0;
+                  flc[j][v] = (t < a.T && valid[v] && ((subi >> t) & 1ull)) ? a.mflags[slot_idx_of<kDense>(mi, t, a.E, e[v])] : 0;
           }
           for (int j = 0; j < kFlagChunk; ++j) {
             const int32_t t = t0 + j;
             if (t >= a.T) break;
             if (!((subi >> t) & 1ull)) continue;           // not joined
-            const HbArgs& a = hb_launder(a_);
-            const ctp_t tp = const_tp(a.tp) + t;
-            const bool scored = tp->scored != 0;
-            const double thr = tp->mesh_message_deliveries_threshold;
-            const double mcap = tp->mesh_message_deliveries_cap;
+            // Steady state: a mesh inside [Dlo, Dhi] with Dout outbound peers and
+            // no negative score, on a tick without opportunistic grafting, is
+            // left as it is -- the maintenance below would graft and prune
+            // nothing, store nothing and send no control.  Lane groups test
+            // that once for the whole wave (kSteady) and skip it in one uniform
+            // branch: of C3's (observer, topic) pairs about 1 % change per tick.
+            // The maintenance's own per-topic state -- the topic's score
+            // parameters, the score records' places, the lazily loaded backoff
+            // -- is then set up behind the test; the hub classes have no test
+            // and set it up here, in the order they always did.
+            constexpr bool kSteady = Grp::kSteadyTest;
             int64_t i[V];
             ScoreFlags sf[V];
             uint8_t fl[V], fl0[V], ctl[V];
             // backoff is only consulted when a graft selection or a prune
             // happens, so it is loaded lazily (steady-state ticks read none)
             int64_t bo[V];
-            bool have_bo[V], bo_dirty[V], tpeer[V], m[V], cand[V], sel[V];
+            bool have_bo[V], bo_dirty[V], tpeer[V], m[V], cand[V];
+            bool scored = false;
+            double thr = 0.0, mcap = 0.0;
+            auto topic_params = [&](const HbArgs& a) {
+                const ctp_t tp = const_tp(a.tp) + t;
+                scored = tp->scored != 0;
+                thr = tp->mesh_message_deliveries_threshold;
+                mcap = tp->mesh_message_deliveries_cap;
+            };
+            const HbArgs& a0 = hb_launder(a_);
+            if constexpr (!kSteady) topic_params(a0);
 #pragma unroll
             for (int v = 0; v < V; ++v) {
-                i[v] = slot_idx(mi, t, a.E, e[v]);
-                sf[v].at(mj[v], t, a.E, rv[v]);
+                i[v] = slot_idx_of<kDense>(mi, t, a0.E, e[v]);
+                if constexpr (!kSteady) sf[v].template at<kDense>(mj[v], t, a0.E, rv[v]);
                 fl[v] = flc[j][v];
                 fl0[v] = fl[v];
-                bo[v] = 0;
-                have_bo[v] = bo_dirty[v] = false;
+                if constexpr (!kSteady) { bo[v] = 0; have_bo[v] = bo_dirty[v] = false; }
                 tpeer[v] = valid[v] && conn[v] && ((subj[v] >> t) & 1ull);
                 m[v] = valid[v] && (fl[v] & GSIM_TF_MESH);
                 ctl[v] = 0;
+            }
+            bool maintain = true;
+            if constexpr (kSteady) {
+                static_assert(V == 1, "lane groups hold one row position per lane");
+                maintain = g.opp_tick ||
+                           !g.steady(m[0], m[0] && outb[0], m[0] && S[0] < 0, a0.Dlo, a0.Dhi, a0.Dout);
+            }
+            if (maintain) {
+#if GSIM_DIAG_HB == 2
+            if constexpr (kSteady) if (__ffsll((long long)__ballot(true)) - 1 == (int)(threadIdx.x & 63)) atomicAdd(&g_hb_sel[3], 1ull);
+#endif
+            // (behind the test the arguments are read again, so that the loads of
+            // the maintenance's pointers stay inside this branch)
+            const HbArgs& a = hb_launder_if<kSteady>(a_, a0);
+            bool sel[V];
+            if constexpr (kSteady) {
+                topic_params(a);
+#pragma unroll
+                for (int v = 0; v < V; ++v) {
+                    sf[v].template at<kDense>(mj[v], t, a.E, rv[v]);
+                    bo[v] = 0;
+                    have_bo[v] = bo_dirty[v] = false;
+                }
             }
             auto need_bo = [&](int v) {
                 if (!have_bo[v]) {
@@ -1114,7 +1255,10 @@ __device__ __forceinline__ void hb_observer(const HbArgs& a_, Grp& g, int64_t ob
 
             // opportunistic grafting (1520-1552)
             l = g.count(m);
-            if (a.opp_ticks && a.tick % a.opp_ticks == 0 && l > 1) {
+            // (lane groups hold the tick's flag: their steady-state test reads it for
+            // every topic, a 64-bit modulo each time otherwise; held across the topics
+            // of a hub class it costs registers, k_heartbeat_hub<256, 2> a wave per SIMD)
+            if ((kSteady ? g.opp_tick : (a.opp_ticks && a.tick % a.opp_ticks == 0)) && l > 1) {
                 int rank[V];
 #pragma unroll
                 for (int v = 0; v < V; ++v) rank[v] = 0;
@@ -1163,6 +1307,7 @@ __device__ __forceinline__ void hb_observer(const HbArgs& a_, Grp& g, int64_t ob
                 sf[v].store(a);
                 if (bo_dirty[v]) a.backoff[i[v]] = bo[v];
             }
+            }
           {
             const HbArgs& a = hb_launder(a_);   // (the mesh maintenance's pointers are dead here)
             // the delivery's mesh mask of this row and topic (mesh or direct
@@ -1199,17 +1344,19 @@ __device__ __forceinline__ void hb_observer(const HbArgs& a_, Grp& g, int64_t ob
                 for (int v = 0; v < V; ++v)
                     if (valid[v]) a.gsel[i[v]] = gs[v] ? 1 : 0;
             }
+            if (maintain) {                     // (else no control to send: ctl is zero)
             bool pxc[V];
 #pragma unroll
             for (int v = 0; v < V; ++v) {
-                if (valid[v] && ctl[v] && slot_has(mj[v], t)) {
-                    const int64_t r = slot_idx(mj[v], t, a.E, rv[v]);   // the receiver's row
+                if (valid[v] && ctl[v] && slot_has_of<kDense>(mj[v], t)) {
+                    const int64_t r = slot_idx_of<kDense>(mj[v], t, a.E, rv[v]);   // the receiver's row
                     a.ctl_out[r] = (uint8_t)(a.ctl_out[r] | ctl[v]);
                     atomicOr(reinterpret_cast<unsigned long long*>(a.cany_out + col[v]), 1ull << t);
                 }
                 pxc[v] = (ctl[v] & GSIM_CTL_PX) != 0;
             }
             if (a.do_px && g.any(pxc)) pxt |= 1ull << t;
+            }
           }
           }
         }
@@ -1228,8 +1375,9 @@ __device__ __forceinline__ void hb_observer(const HbArgs& a_, Grp& g, int64_t ob
 // W-lane groups: W = 64 one observer per wavefront, W = 32 two, W = 16 four
 // (rows of at most W connections; every VALU instruction serves G observers).
 // rows: the observers of one row-length class (a list), or nullptr for the
-// nrows observers from obs_base on.
-template <int W>
+// nrows observers from obs_base on.  Dense: the instance for a network without
+// slot masks (HbArgs::smask null), where a topic's plane is its number.
+template <int W, bool Dense>
 // waves per SIMD the register budget is fitted to: 5 for W = 32 / 64 (C3's
 // k_heartbeat<32>: 96 VGPRs with 10 spilled, 7.91 -> 6.81 ms per tick against 4
 // waves at 106, 7.13 at 6; gpurun_out/r04pab, r04q), 4 for W = 16 (c5's
@@ -1251,7 +1399,8 @@ void k_heartbeat(HbArgs a, const uint32_t* rows, int64_t nrows, int64_t obs_base
 {
     constexpr int G = 64 / W;
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    WaveGroup<W> g(lane);
+    WaveGroup<W, Dense> g(lane);
+    g.opp_tick = a.opp_ticks && a.tick % a.opp_ticks == 0;     // (1520)
     for (int64_t o0 = ((int64_t)blockIdx.x * 4 + wid) * G; o0 < nrows; o0 += (int64_t)gridDim.x * 4 * G) {
         const bool ovalid = o0 + g.grp < nrows;
         const int64_t obs = !ovalid ? 0 : rows ? (int64_t)rows[o0 + g.grp] : obs_base + o0 + g.grp;
@@ -2807,25 +2956,26 @@ int gsim_heartbeat(gsim_handle* h, uint64_t tick, int64_t now)
     // independent within a heartbeat, so the classes run one after the other)
     const Extra* x = h->x;
     const int64_t nown = h->ohi() - h->olo();
+    // (the dense instances where the network has no slot masks)
+    auto lanes = [&](auto w, const uint32_t* r, int64_t n, int64_t base) {
+        constexpr int W = decltype(w)::value;
+        const dim3 grid(grid_rows((n + 64 / W - 1) / (64 / W)));
+        if (a.smask) hipLaunchKernelGGL((k_heartbeat<W, false>), grid, dim3(256), 0, h->stream, a, r, n, base);
+        else hipLaunchKernelGGL((k_heartbeat<W, true>), grid, dim3(256), 0, h->stream, a, r, n, base);
+    };
+    using std::integral_constant;
     if (x->n16 == nown && !x->d_rows) {   // one class: the owned rows in order
-        hipLaunchKernelGGL(k_heartbeat<16>, dim3(grid_rows((nown + 3) / 4)), dim3(256), 0, h->stream, a, nullptr, nown,
-                           h->olo());
+        lanes(integral_constant<int, 16>{}, nullptr, nown, h->olo());
     } else if (x->n32 == nown && !x->d_rows) {
-        hipLaunchKernelGGL(k_heartbeat<32>, dim3(grid_rows((nown + 1) / 2)), dim3(256), 0, h->stream, a, nullptr, nown,
-                           h->olo());
+        lanes(integral_constant<int, 32>{}, nullptr, nown, h->olo());
     } else if (x->n64 == nown && !x->d_rows) {
-        hipLaunchKernelGGL(k_heartbeat<64>, dim3(grid_rows(nown)), dim3(256), 0, h->stream, a, nullptr, nown, h->olo());
+        lanes(integral_constant<int, 64>{}, nullptr, nown, h->olo());
     } else {
         const uint32_t* r = x->d_rows;
-        if (x->n8) hipLaunchKernelGGL(k_heartbeat<8>, dim3(grid_rows((x->n8 + 7) / 8)), dim3(256), 0, h->stream,
-                                      a, r, x->n8, (int64_t)0);
-        if (x->n16 > x->n8)
-            hipLaunchKernelGGL(k_heartbeat<16>, dim3(grid_rows((x->n16 - x->n8 + 3) / 4)), dim3(256), 0, h->stream,
-                               a, r + x->n8, x->n16 - x->n8, (int64_t)0);
-        if (x->n32) hipLaunchKernelGGL(k_heartbeat<32>, dim3(grid_rows((x->n32 + 1) / 2)), dim3(256), 0, h->stream,
-                                       a, r + x->n16, x->n32, (int64_t)0);
-        if (x->n64) hipLaunchKernelGGL(k_heartbeat<64>, dim3(grid_rows(x->n64)), dim3(256), 0, h->stream,
-                                       a, r + x->n16 + x->n32, x->n64, (int64_t)0);
+        if (x->n8) lanes(integral_constant<int, 8>{}, r, x->n8, 0);
+        if (x->n16 > x->n8) lanes(integral_constant<int, 16>{}, r + x->n8, x->n16 - x->n8, 0);
+        if (x->n32) lanes(integral_constant<int, 32>{}, r + x->n16, x->n32, 0);
+        if (x->n64) lanes(integral_constant<int, 64>{}, r + x->n16 + x->n32, x->n64, 0);
         // hubs: one block per observer
         const uint32_t* rh = r + x->n16 + x->n32 + x->n64;
         // one block per class row: (threads, row positions per thread) by class (kHub*)
@@ -3169,8 +3319,13 @@ extern "C" int gsim_diag_hb_counts(gsim_handle* h, uint64_t* out4)
     if (!h || !out4) return GSIM_EINVAL;
     if (hipStreamSynchronize(h->stream) != hipSuccess) return GSIM_EDEVICE;
     unsigned long long z[4] = {0, 0, 0, 0};
+#if GSIM_DIAG_HB == 2
+    if (hipMemcpyFromSymbol(out4, HIP_SYMBOL(g_hb_sel), sizeof(z)) != hipSuccess) return GSIM_EDEVICE;
+    if (hipMemcpyToSymbol(HIP_SYMBOL(g_hb_sel), z, sizeof(z)) != hipSuccess) return GSIM_EDEVICE;
+#else
     if (hipMemcpyFromSymbol(out4, HIP_SYMBOL(g_hb_diag), sizeof(z)) != hipSuccess) return GSIM_EDEVICE;
     if (hipMemcpyToSymbol(HIP_SYMBOL(g_hb_diag), z, sizeof(z)) != hipSuccess) return GSIM_EDEVICE;
+#endif
     return GSIM_OK;
 }
 #endif

@@ -25,7 +25,7 @@ timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/
   -- python3 "$ROOT/bench.py" --steps "$STEPS" --warmup 3 --full --no-cpu-baseline ${BENCH_ARGS:-} > "$OUT/prof.json" 2> "$OUT/prof.err" \
   || { echo "prof rc=$?"; tail -20 "$OUT/prof.err"; exit 1; }
 python3 "$ROOT/tools/trace_summary.py" "$OUT/prof/s_kernel_trace.csv" 1 > "$OUT/prof_summary.txt"; head -14 "$OUT/prof_summary.txt"
-KRE="${KRE:-k_refresh_score<true, true>|k_send_tm|k_commit|k_heartbeat<32>}"
+KRE="${KRE:-k_refresh_score<true, true>|k_send_tm|k_commit|k_heartbeat<32}"
 pass() {
   local name="$1"; shift
   timeout -s KILL 150 rocprofv3 --kernel-trace --pmc "$@" --kernel-include-regex "$KRE" -d "$OUT/pmc_$name" -o p \

@@ -1,5 +1,5 @@
 #!/bin/bash
-# GPU: k_heartbeat<32> instruction counts at C3 (one SQ counter pass,
+# GPU: k_heartbeat<32, ...> instruction counts at C3 (one SQ counter pass,
 # kernel-trace only), summed per launch: the VALU-issue roofline's input.
 set -uo pipefail
 TAG="${1:-pmc_hb}"
@@ -9,7 +9,7 @@ mkdir -p "$OUT"
 export TMPDIR=/tmp
 cd /tmp
 timeout -s KILL 240 rocprofv3 --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_INSTS_LDS SQ_BUSY_CYCLES SQ_WAVE_CYCLES \
-  --kernel-include-regex "k_heartbeat<32>" -d "$OUT/hb_sq" -o run --output-format csv \
+  --kernel-include-regex "k_heartbeat<32" -d "$OUT/hb_sq" -o run --output-format csv \
   -- python3 "$ROOT/bench.py" --steps 3 --warmup 2 --full --no-cpu-baseline > "$OUT/hb_sq.log" 2>&1 || { echo "rc=$?"; tail -5 "$OUT/hb_sq.log"; exit 1; }
 python3 - "$OUT" <<'PY'
 import csv, collections, glob, sys

@@ -76,7 +76,7 @@ def main():
         source=src)
     data[wl + ":send_req"] = dict(reqs(vs), **l2(vs), kernel=ks, ceiling_req_per_s=54e9, ceiling_source=PROBE,
                                   commit=dict(reqs(vc), **l2(vc), kernel=kc), source=src)
-    kh, vh = find(pmc, "k_heartbeat<32>")
+    kh, vh = find(pmc, "k_heartbeat<32")       # <32> before the dense instances, <32, true> since
     data[wl + ":hb_valu"] = dict(valu_insts_per_launch=vh["SQ_INSTS_VALU"], salu_insts_per_launch=vh["SQ_INSTS_SALU"],
                                  waves_per_launch=vh["SQ_WAVES"], peak_wave_insts_per_s=256 * 4 * 2.4e9 / 2,
                                  peak_source=("MI355X_MICROARCH.md: 256 CUs x 4 SIMDs x 2.4 GHz, a wave64 VALU op "
