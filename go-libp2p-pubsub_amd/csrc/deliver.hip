@@ -4005,6 +4005,19 @@ bool deliver_trace_view(gsim_handle* h, TraceView* v)
     return true;
 }
 
+bool deliver_report_view(gsim_handle* h, ReportView* v)
+{
+    Deliver* d = h->dl;
+    if (!d) return false;
+    v->cells = deliver_cells(d); v->ncells = (int64_t)d->n_cells;
+    v->mtopic = d->d_mtopic; v->morigin = d->d_morigin; v->minv = d->d_minv; v->mlat = d->d_mlat; v->mid = d->d_mid;
+    v->mpub = d->d_mpub; v->slot_last = d->d_slot_last;
+    v->ring = d->cfg.ring; v->T = h->t; v->n = h->n;
+    v->rlo = (uint32_t)h->olo(); v->rhi = (uint32_t)h->ohi();
+    v->sub = h->d_sub;
+    return true;
+}
+
 int64_t deliver_last_round_time(gsim_handle* h)
 {
     const Deliver* d = h->dl;

@@ -1264,6 +1264,7 @@ int gsim_destroy(gsim_handle* h)
     free_gater(h);
     free_deliver(h);
     trace_release(h);
+    report_release(h);
     dfree(h->d_tp);
     dfree(h->d_flags);
     for (auto& ev : h->ev)

@@ -444,6 +444,8 @@ struct TraceRef {
 };
 
 struct Gater;   // the peer gater's state (gater.hip)
+struct Report;  // the propagation report's device scratch (report.hip)
+using MsgReport = struct ::gsim_msg_report;   // (the call gsim_msg_report hides the struct's name in C++)
 
 // The peer gater's device state as the delivery kernels see it (gater.hip;
 // act == nullptr: the gater is off).
@@ -580,6 +582,7 @@ struct gsim_handle {
     gsim::ShardCtx* sh = nullptr;   // graph-sharded network: this handle is one shard (shard.hip)
     struct gsim::Gater* gt = nullptr;   // peer gater (gater.hip), nullptr: off
     gsim::TraceRef trace;           // gsim_trace_config (trace.hip)
+    gsim::Report* rp = nullptr;     // gsim_msg_report scratch (report.hip), allocated at the first call
 
     // owned peers / observer rows (all of them unless sharded)
     int64_t olo() const { return sh ? sh->own_lo : 0; }
@@ -713,6 +716,21 @@ struct TraceView {
     const int64_t* roff;
 };
 bool deliver_trace_view(gsim_handle* h, TraceView* v);
+// report.hip: what the propagation report reads of the message state (gsim_msg_report)
+struct ReportView {
+    gsim::Cells cells;          // the seen-set: slot m's cells are cell[cbase[m] .. cbase[m + 1]) (the last: ncells)
+    int64_t ncells;
+    const uint32_t *mtopic, *morigin;
+    const uint8_t *minv, *mlat;
+    const uint64_t* mid;
+    const int32_t *mpub, *slot_last;
+    int32_t ring, T;
+    int64_t n;                  // local peers
+    uint32_t rlo, rhi;          // owned peers (all of them unless sharded)
+    const uint64_t* sub;        // [n] announced topics
+};
+bool deliver_report_view(gsim_handle* h, ReportView* v);   // false before gsim_msgs_init
+void report_release(gsim_handle* h);  // report.hip
 int64_t deliver_last_round_time(gsim_handle* h);   // time of the last round run (INT64_MAX: none yet)
 void trace_release(gsim_handle* h);   // trace.hip
 // round stages (deliver.hip; gsim_round runs them in order, a sharded group

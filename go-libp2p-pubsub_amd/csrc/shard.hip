@@ -38,6 +38,7 @@
 
 #include "gsim.h"
 #include "gsim_internal.h"
+#include "report_merge.h"
 #include "shard_layout.h"
 
 using namespace gsim;
@@ -2179,6 +2180,47 @@ int gsim_group_census(gsim_group* g, int64_t* out8)
 {
     if (!g || !out8) return GSIM_EINVAL;
     return group_sum(g, gsim_census, 8, out8);
+}
+
+// gsim_msg_report over the group: every local shard reports the peers it owns
+// and the rows are merged by slot on the host (report_merge.cpp).  A slot's
+// message is the same on every shard (gsim_group_publish hands every shard
+// every publication).
+int gsim_group_msg_report(gsim_group* g, int64_t round_lo, int64_t round_hi, struct gsim_msg_report* out, int64_t cap,
+                          int64_t* n)
+{
+    if (!g || !n || cap < 0) return GSIM_EINVAL;
+    *n = 0;
+    if (!g->msgs || g->hs.empty()) return g->fail(GSIM_ESTATE, "gsim_group_msgs_init not called");
+    auto call = [&](gsim_handle* h, MsgReport* o, int64_t c, int64_t* k) {
+        const int rc = gsim_msg_report(h, round_lo, round_hi, o, c, k);
+        return rc ? g->take(h, rc) : GSIM_OK;               // (a shard's delivery error flags included)
+    };
+    int64_t cnt = 0;
+    int rc = call(g->hs[0], nullptr, 0, &cnt);             // the same selection on every shard
+    if (rc) return rc;
+    *n = cnt;
+    if (!out || cap == 0) return GSIM_OK;
+    if (cap < cnt) return g->fail(GSIM_ERANGE, "output buffer too small for the selected messages");
+    std::vector<std::vector<MsgReport>> parts(g->hs.size());
+    for (size_t l = 0; l < g->hs.size(); ++l) {
+        parts[l].resize((size_t)cnt);
+        int64_t got = 0;
+        rc = cnt ? call(g->hs[l], parts[l].data(), cnt, &got) : call(g->hs[l], nullptr, 0, &got);
+        if (rc) return rc;
+        if (got != cnt) return g->fail(GSIM_ESTATE, "the shards disagree about the messages in the ring");
+    }
+    std::vector<const MsgReport*> pp;
+    std::vector<const uint32_t*> gp;
+    std::vector<size_t> gn;
+    for (size_t l = 0; l < g->hs.size(); ++l) {
+        pp.push_back(parts[l].data());
+        gp.push_back(g->gid[l].data());
+        gn.push_back(g->gid[l].size());
+    }
+    if (merge_reports(pp.data(), gp.data(), gn.data(), pp.size(), (size_t)cnt, out))
+        return g->fail(GSIM_ESTATE, "the shards disagree about a slot's message");
+    return GSIM_OK;
 }
 
 int gsim_group_synchronize(gsim_group* g)

@@ -117,6 +117,21 @@ class CMsg(Structure):
 # numpy view of gsim_msg (24 bytes)
 MSG_DTYPE = [("id", "<u8"), ("topic", "<u4"), ("origin", "<u4"), ("verdict", "u1"), ("vdelay", "u1"),
              ("_pad", "u1", (6,))]
+REPORT_BINS = 32        # gsim.h GSIM_REPORT_BINS
+
+
+class CMsgReport(Structure):
+    """struct gsim_msg_report (176 bytes): one message's reach and latency histogram."""
+    _fields_ = [("id", c_uint64), ("pub_round", c_int64), ("slot", c_uint32), ("topic", c_uint32),
+                ("origin", c_uint32), ("reached", c_uint32), ("subscribers", c_uint32), ("max_latency", c_uint32),
+                ("verdict", ctypes.c_uint8), ("vdelay", ctypes.c_uint8), ("_pad", ctypes.c_uint8 * 6),
+                ("hist", c_uint32 * REPORT_BINS)]
+
+
+# numpy view of struct gsim_msg_report
+MSG_REPORT_DTYPE = [("id", "<u8"), ("pub_round", "<i8"), ("slot", "<u4"), ("topic", "<u4"), ("origin", "<u4"),
+                    ("reached", "<u4"), ("subscribers", "<u4"), ("max_latency", "<u4"), ("verdict", "u1"),
+                    ("vdelay", "u1"), ("_pad", "u1", (6,)), ("hist", "<u4", (REPORT_BINS,))]
 MAX_VDELAY = 7          # gsim.h GSIM_MAX_VDELAY
 # gsim.h GSIM_VERDICT_*: the validation verdict of a message at every receiver
 VERDICT_ACCEPT, VERDICT_REJECT, VERDICT_IGNORE, VERDICT_THROTTLE, VERDICT_SIGNATURE = 0, 1, 2, 3, 4
@@ -256,6 +271,7 @@ SIGNATURES = [
     ("gsim_step", c_int32, [c_void_p, c_uint64, c_int32, c_void_p, c_void_p]),
     ("gsim_host_sync_count", c_int32, [c_void_p]),
     ("gsim_msg_stats", c_int32, [c_void_p, c_void_p]),
+    ("gsim_msg_report", c_int32, [c_void_p, c_int64, c_int64, c_void_p, c_int64, POINTER(c_int64)]),
     ("gsim_set_peer_behaviour", c_int32, [c_void_p, c_void_p]),
     ("gsim_gossip_stats", c_int32, [c_void_p, c_void_p]),
     ("gsim_set_connections", c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int64]),
@@ -315,6 +331,7 @@ SIGNATURES = [
     ("gsim_group_msg_stats", c_int32, [c_void_p, c_void_p]),
     ("gsim_group_gossip_stats", c_int32, [c_void_p, c_void_p]),
     ("gsim_group_census", c_int32, [c_void_p, c_void_p]),
+    ("gsim_group_msg_report", c_int32, [c_void_p, c_int64, c_int64, c_void_p, c_int64, POINTER(c_int64)]),
     ("gsim_group_synchronize", c_int32, [c_void_p]),
     ("gsim_group_profile", c_int32, [c_void_p, c_int32]),
     ("gsim_group_profile_read", c_int32, [c_void_p, c_void_p, c_void_p, c_int32]),

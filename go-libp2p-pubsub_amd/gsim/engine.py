@@ -428,6 +428,22 @@ class Engine:
         self._check(self.lib.gsim_msg_stats(self.h, _ptr(out)))
         return [int(x) for x in out]
 
+    # struct gsim_msg_report
+    MSG_REPORT_DTYPE = np.dtype(_abi.MSG_REPORT_DTYPE)
+
+    def msg_report(self, round_lo: int = 0, round_hi: int | None = None) -> np.ndarray:
+        """Reach and latency histogram of every message still in the ring that
+        was published in [round_lo, round_hi) (None: no upper bound), as
+        MSG_REPORT_DTYPE rows ordered by (pub_round, slot) (gsim_msg_report;
+        helpers over the array: gsim.report)."""
+        hi = (1 << 63) - 1 if round_hi is None else int(round_hi)
+        n = ctypes.c_int64(0)
+        self._check(self.lib.gsim_msg_report(self.h, int(round_lo), hi, None, 0, ctypes.byref(n)))
+        out = np.zeros(n.value, dtype=self.MSG_REPORT_DTYPE)
+        if n.value:
+            self._check(self.lib.gsim_msg_report(self.h, int(round_lo), hi, _ptr(out), n.value, ctypes.byref(n)))
+        return out[:n.value]
+
     def read(self, f: int) -> np.ndarray:
         out = np.empty(self.field_shape(f), dtype=_FIELD_DTYPES[f])
         self._check(self.lib.gsim_read_field(self.h, f, _ptr(out), out.nbytes))

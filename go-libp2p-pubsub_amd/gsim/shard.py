@@ -421,6 +421,19 @@ class ShardedEngine:
         self._check(self.lib.gsim_group_trace_read(self.g, _ptr(out) if n.value else None, n.value, ctypes.byref(n)))
         return out[:n.value]
 
+    def msg_report(self, round_lo: int = 0, round_hi: int | None = None) -> np.ndarray:
+        """Engine.msg_report over the shards of this process, merged by slot,
+        origins in global ids (gsim_group_msg_report; one shard per process:
+        the local shards' partial sums)."""
+        from .engine import Engine
+        hi = (1 << 63) - 1 if round_hi is None else int(round_hi)
+        n = ctypes.c_int64(0)
+        self._check(self.lib.gsim_group_msg_report(self.g, int(round_lo), hi, None, 0, ctypes.byref(n)))
+        out = np.zeros(n.value, dtype=Engine.MSG_REPORT_DTYPE)
+        if n.value:
+            self._check(self.lib.gsim_group_msg_report(self.g, int(round_lo), hi, _ptr(out), n.value, ctypes.byref(n)))
+        return out[:n.value]
+
     def msg_stats(self) -> list:
         out = np.zeros(4, dtype=np.int64)
         self._check(self.lib.gsim_group_msg_stats(self.g, _ptr(out)))

@@ -440,6 +440,39 @@ int gsim_step(gsim_handle* h, uint64_t tick, int32_t n_ticks, const gsim_msg* ms
  * could still be gossiped (results are then incomplete). */
 int gsim_msg_stats(gsim_handle* h, int64_t* out4);
 
+/* Propagation report: how far each message still in the ring got, and how
+ * fast (the reach of DeliverMessage, score.go:702-726, per message).  One row
+ * per message whose publication round lies in [round_lo, round_hi), ordered
+ * by (pub_round, slot); never-published slots are left out and a republished
+ * slot reports its current message only.  A peer's latency is its first-seen
+ * round minus pub_round, the first-seen round being what GSIM_F_SEEN shows
+ * (the high word of the committed seen-set cell): with vdelay > 0 that is the
+ * round the receiver's validation completes, not the
+ * round the copy arrived.  The origin's own cell falls in bin 0;
+ * sum(hist) == reached.  The histograms are reduced on the device from the
+ * seen-set cells (no [ring][N] view is built). */
+#define GSIM_REPORT_BINS 32
+struct gsim_msg_report {
+    uint64_t id;            /* gsim_msg.id of the slot's message                          */
+    int64_t  pub_round;     /* round it was published in                                  */
+    uint32_t slot, topic;
+    uint32_t origin;        /* peer id (global id on a group)                             */
+    uint32_t reached;       /* peers with a committed cell, the origin included           */
+    uint32_t subscribers;   /* peers announcing `topic` now (gs.p.topics), the denominator */
+    uint32_t max_latency;   /* largest latency among the reached peers (exact, not binned) */
+    uint8_t  verdict, vdelay, _pad[6];
+    uint32_t hist[GSIM_REPORT_BINS]; /* hist[d], d < 31: peers with latency d; hist[31]: latency >= 31 */
+};  /* 176 bytes, hist at offset 48.  A struct tag without a typedef: the call below has
+       the same name, and C keeps typedef names and function names in one namespace */
+/* *n is always set to the number of selected messages; out == NULL or
+ * cap == 0 counts only; 0 < cap < *n: GSIM_ERANGE, nothing written.
+ * GSIM_ESTATE before gsim_msgs_init.  Pending claims are committed first, so
+ * the call may follow any round.  Synchronizes; returns gsim_msg_stats's
+ * GSIM_ERANGE / GSIM_ESTATE (rows written) when the delivery error flags are
+ * set. */
+int gsim_msg_report(gsim_handle* h, int64_t round_lo, int64_t round_hi,
+                    struct gsim_msg_report* out, int64_t cap, int64_t* n);
+
 /* Per-peer behaviour flags for adversarial configurations:
  * GSIM_BEHAVE_IGNORE_IWANT = the peer advertises (IHAVE) but never answers
  * IWANT (gossipsub_spam_test.go:134-286), so the requesters' promises break
@@ -794,6 +827,16 @@ int gsim_group_state_written(gsim_group* g);
 int gsim_group_msg_stats(gsim_group* g, int64_t* out4);
 int gsim_group_gossip_stats(gsim_group* g, int64_t* out4);
 int gsim_group_census(gsim_group* g, int64_t* out8);
+/* gsim_msg_report over a sharded network: every local shard reports the
+ * peers it owns and the rows are merged by slot (hist, reached, subscribers
+ * summed; max_latency the maximum); origin is the global id.  GSIM_ESTATE if
+ * the shards disagree about a slot's message.  With one shard per process
+ * (RCCL / host transports) the rows hold the local shards' partial sums, as
+ * gsim_group_read_field holds a rank's rows, and origin is 0xFFFFFFFF where
+ * the publishing peer is neither owned by nor a neighbour of the rank's
+ * shard. */
+int gsim_group_msg_report(gsim_group* g, int64_t round_lo, int64_t round_hi,
+                          struct gsim_msg_report* out, int64_t cap, int64_t* n);
 int gsim_group_synchronize(gsim_group* g);
 /* WithPeerScoreInspect over a sharded network (score.go:152-180, 448-500):
  * the whole network's view, filled from the rows this process's shards own
