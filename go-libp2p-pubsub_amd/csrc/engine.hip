@@ -739,6 +739,7 @@ void free_graph(gsim_handle* h)
     dfree(h->d_bp); dfree(h->d_estate); dfree(h->d_expire); dfree(h->d_p6); dfree(h->d_p6row); dfree(h->d_churn); h->churn_cap = 0; dfree(h->d_churn_mark); dfree(h->d_score);
     dfree(h->d_backoff); dfree(h->d_rstate); dfree(h->d_dstate); dfree(h->d_mcnt); dfree(h->d_pen);
     dfree(h->d_smask);
+    netreport_release(h);        // peer classes are the old graph's
     h->smask.clear();
     h->S = 0;
     h->bytes_allocated = 0;

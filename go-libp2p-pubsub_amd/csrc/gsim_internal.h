@@ -445,6 +445,7 @@ struct TraceRef {
 
 struct Gater;   // the peer gater's state (gater.hip)
 struct Report;  // the propagation report's device scratch (report.hip)
+struct NetReport;  // the network report's peer classes and device scratch (netreport.hip)
 using MsgReport = struct ::gsim_msg_report;   // (the call gsim_msg_report hides the struct's name in C++)
 
 // The peer gater's device state as the delivery kernels see it (gater.hip;
@@ -583,6 +584,7 @@ struct gsim_handle {
     struct gsim::Gater* gt = nullptr;   // peer gater (gater.hip), nullptr: off
     gsim::TraceRef trace;           // gsim_trace_config (trace.hip)
     gsim::Report* rp = nullptr;     // gsim_msg_report scratch (report.hip), allocated at the first call
+    gsim::NetReport* nr = nullptr;  // gsim_set_peer_classes / gsim_net_report (netreport.hip); a new graph drops it
 
     // owned peers / observer rows (all of them unless sharded)
     int64_t olo() const { return sh ? sh->own_lo : 0; }
@@ -731,6 +733,11 @@ struct ReportView {
 };
 bool deliver_report_view(gsim_handle* h, ReportView* v);   // false before gsim_msgs_init
 void report_release(gsim_handle* h);  // report.hip
+// netreport.hip: the network report (gsim_net_report)
+void netreport_release(gsim_handle* h);
+// one class per local peer (nullptr: all 0); C > 0: the report's class count (a
+// shard takes the whole network's), C = 0: 1 + the largest class given
+int netreport_set_classes(gsim_handle* h, const uint8_t* cls, int C);
 int64_t deliver_last_round_time(gsim_handle* h);   // time of the last round run (INT64_MAX: none yet)
 void trace_release(gsim_handle* h);   // trace.hip
 // round stages (deliver.hip; gsim_round runs them in order, a sharded group

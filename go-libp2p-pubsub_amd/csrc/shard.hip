@@ -38,6 +38,7 @@
 
 #include "gsim.h"
 #include "gsim_internal.h"
+#include "netreport_merge.h"
 #include "report_merge.h"
 #include "shard_layout.h"
 
@@ -2220,6 +2221,73 @@ int gsim_group_msg_report(gsim_group* g, int64_t round_lo, int64_t round_hi, str
     }
     if (merge_reports(pp.data(), gp.data(), gn.data(), pp.size(), (size_t)cnt, out))
         return g->fail(GSIM_ESTATE, "the shards disagree about a slot's message");
+    return GSIM_OK;
+}
+
+// Peer classes by global id: every shard gets its local peers' (its ghosts
+// too: a mesh link's or a score's other end may be one) and the whole
+// network's class count, so that the shards' rows line up.
+int gsim_group_set_peer_classes(gsim_group* g, const uint8_t* cls)
+{
+    if (!g) return GSIM_EINVAL;
+    if (g->hs.empty() || g->N == 0) return g->fail(GSIM_ESTATE, "no graph loaded (call gsim_group_load_graph first)");
+    int C = 1;
+    if (cls)
+        for (int64_t p = 0; p < g->N; ++p) {
+            if (cls[p] >= GSIM_NET_CLASSES) return g->fail(GSIM_EINVAL, "peer class out of range (must be below GSIM_NET_CLASSES)");
+            C = std::max<int>(C, cls[p] + 1);
+        }
+    for (size_t l = 0; l < g->hs.size(); ++l) {
+        int rc;
+        if (!cls) {
+            rc = netreport_set_classes(g->hs[l], nullptr, 1);
+        } else {
+            std::vector<uint8_t> v(g->gid[l].size());
+            for (size_t x = 0; x < v.size(); ++x) v[x] = cls[g->gid[l][x]];
+            rc = netreport_set_classes(g->hs[l], v.data(), C);
+        }
+        if (rc) return g->take(g->hs[l], rc);
+    }
+    return GSIM_OK;
+}
+
+// gsim_net_report over the group: every local shard reports the observers it
+// owns; the rows are merged on the host (netreport_merge.cpp).
+int gsim_group_net_report(gsim_group* g, const double* edges, int32_t n_edges, struct gsim_mesh_row* mesh,
+                          int64_t mesh_cap, int64_t* n_mesh, struct gsim_score_row* scores, int64_t score_cap,
+                          int64_t* n_scores)
+{
+    if (!g || !n_mesh || !n_scores || mesh_cap < 0 || score_cap < 0) return GSIM_EINVAL;
+    *n_mesh = *n_scores = 0;
+    if (g->hs.empty()) return g->fail(GSIM_ESTATE, "the group holds no shard");
+    int64_t nm = 0, ns = 0;
+    int rc = gsim_net_report(g->hs[0], edges, n_edges, nullptr, 0, &nm, nullptr, 0, &ns);   // validates; counts
+    *n_mesh = nm;
+    *n_scores = ns;
+    if (rc) return g->take(g->hs[0], rc);
+    const bool want_mesh = mesh && mesh_cap > 0, want_scores = scores && score_cap > 0;
+    if ((want_mesh && mesh_cap < nm) || (want_scores && score_cap < ns))
+        return g->fail(GSIM_ERANGE, "gsim_group_net_report: output buffer too small");
+    if (!want_mesh && !want_scores) return GSIM_OK;
+    const size_t L = g->hs.size();
+    std::vector<std::vector<gsim_mesh_row>> mp(L);
+    std::vector<std::vector<gsim_score_row>> sp(L);
+    std::vector<const gsim_mesh_row*> mpp;
+    std::vector<const gsim_score_row*> spp;
+    for (size_t l = 0; l < L; ++l) {
+        if (want_mesh) mp[l].resize((size_t)nm);
+        if (want_scores) sp[l].resize((size_t)ns);
+        int64_t gm = 0, gs = 0;
+        rc = gsim_net_report(g->hs[l], edges, n_edges, want_mesh ? mp[l].data() : nullptr, want_mesh ? nm : 0, &gm,
+                             want_scores ? sp[l].data() : nullptr, want_scores ? ns : 0, &gs);
+        if (rc) return g->take(g->hs[l], rc);
+        if (gm != nm || gs != ns) return g->fail(GSIM_ESTATE, "the shards disagree about the report's rows");
+        mpp.push_back(mp[l].data());
+        spp.push_back(sp[l].data());
+    }
+    if (merge_net_reports(want_mesh ? mpp.data() : nullptr, want_scores ? spp.data() : nullptr, L, (size_t)nm, (size_t)ns,
+                          want_mesh ? mesh : nullptr, want_scores ? scores : nullptr))
+        return g->fail(GSIM_ESTATE, "the shards disagree about a report row's key");
     return GSIM_OK;
 }
 

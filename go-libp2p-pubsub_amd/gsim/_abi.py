@@ -132,6 +132,31 @@ class CMsgReport(Structure):
 MSG_REPORT_DTYPE = [("id", "<u8"), ("pub_round", "<i8"), ("slot", "<u4"), ("topic", "<u4"), ("origin", "<u4"),
                     ("reached", "<u4"), ("subscribers", "<u4"), ("max_latency", "<u4"), ("verdict", "u1"),
                     ("vdelay", "u1"), ("_pad", "u1", (6,)), ("hist", "<u4", (REPORT_BINS,))]
+# gsim.h GSIM_NET_*: the network report (gsim_net_report)
+NET_CLASSES, NET_DEG_BINS, NET_OUT_BINS, NET_SCORE_BINS = 4, 32, 8, 16
+
+
+class CMeshRow(Structure):
+    """struct gsim_mesh_row (232 bytes): one (topic, observer class) of the mesh report."""
+    _fields_ = [("topic", c_uint32), ("cls", c_uint32), ("members", c_uint32), ("max_degree", c_uint32),
+                ("fanout_peers", c_uint32), ("_pad", c_uint32), ("mesh_links", c_uint64 * NET_CLASSES),
+                ("outbound_links", c_uint64), ("fanout_links", c_uint64), ("deg_hist", c_uint32 * NET_DEG_BINS),
+                ("out_hist", c_uint32 * NET_OUT_BINS)]
+
+
+class CScoreRow(Structure):
+    """struct gsim_score_row (176 bytes): one (observer class, subject class) of the score report."""
+    _fields_ = [("obs_cls", c_uint32), ("subj_cls", c_uint32), ("connected", c_uint64), ("retained", c_uint64),
+                ("nan", c_uint64), ("min", c_double), ("max", c_double), ("hist", c_uint64 * NET_SCORE_BINS)]
+
+
+# numpy views of struct gsim_mesh_row / struct gsim_score_row
+MESH_ROW_DTYPE = [("topic", "<u4"), ("cls", "<u4"), ("members", "<u4"), ("max_degree", "<u4"),
+                  ("fanout_peers", "<u4"), ("_pad", "<u4"), ("mesh_links", "<u8", (NET_CLASSES,)),
+                  ("outbound_links", "<u8"), ("fanout_links", "<u8"), ("deg_hist", "<u4", (NET_DEG_BINS,)),
+                  ("out_hist", "<u4", (NET_OUT_BINS,))]
+SCORE_ROW_DTYPE = [("obs_cls", "<u4"), ("subj_cls", "<u4"), ("connected", "<u8"), ("retained", "<u8"),
+                   ("nan", "<u8"), ("min", "<f8"), ("max", "<f8"), ("hist", "<u8", (NET_SCORE_BINS,))]
 MAX_VDELAY = 7          # gsim.h GSIM_MAX_VDELAY
 # gsim.h GSIM_VERDICT_*: the validation verdict of a message at every receiver
 VERDICT_ACCEPT, VERDICT_REJECT, VERDICT_IGNORE, VERDICT_THROTTLE, VERDICT_SIGNATURE = 0, 1, 2, 3, 4
@@ -272,6 +297,9 @@ SIGNATURES = [
     ("gsim_host_sync_count", c_int32, [c_void_p]),
     ("gsim_msg_stats", c_int32, [c_void_p, c_void_p]),
     ("gsim_msg_report", c_int32, [c_void_p, c_int64, c_int64, c_void_p, c_int64, POINTER(c_int64)]),
+    ("gsim_set_peer_classes", c_int32, [c_void_p, c_void_p]),
+    ("gsim_net_report", c_int32, [c_void_p, c_void_p, c_int32, c_void_p, c_int64, POINTER(c_int64), c_void_p,
+                                  c_int64, POINTER(c_int64)]),
     ("gsim_set_peer_behaviour", c_int32, [c_void_p, c_void_p]),
     ("gsim_gossip_stats", c_int32, [c_void_p, c_void_p]),
     ("gsim_set_connections", c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int64]),
@@ -332,6 +360,9 @@ SIGNATURES = [
     ("gsim_group_gossip_stats", c_int32, [c_void_p, c_void_p]),
     ("gsim_group_census", c_int32, [c_void_p, c_void_p]),
     ("gsim_group_msg_report", c_int32, [c_void_p, c_int64, c_int64, c_void_p, c_int64, POINTER(c_int64)]),
+    ("gsim_group_set_peer_classes", c_int32, [c_void_p, c_void_p]),
+    ("gsim_group_net_report", c_int32, [c_void_p, c_void_p, c_int32, c_void_p, c_int64, POINTER(c_int64), c_void_p,
+                                        c_int64, POINTER(c_int64)]),
     ("gsim_group_synchronize", c_int32, [c_void_p]),
     ("gsim_group_profile", c_int32, [c_void_p, c_int32]),
     ("gsim_group_profile_read", c_int32, [c_void_p, c_void_p, c_void_p, c_int32]),

@@ -444,6 +444,33 @@ class Engine:
             self._check(self.lib.gsim_msg_report(self.h, int(round_lo), hi, _ptr(out), n.value, ctypes.byref(n)))
         return out[:n.value]
 
+    # struct gsim_mesh_row / struct gsim_score_row
+    MESH_ROW_DTYPE = np.dtype(_abi.MESH_ROW_DTYPE)
+    SCORE_ROW_DTYPE = np.dtype(_abi.SCORE_ROW_DTYPE)
+
+    def set_peer_classes(self, cls):
+        """One class (< _abi.NET_CLASSES) per peer, None: all class 0; the
+        classes key net_report and change nothing else (gsim_set_peer_classes)."""
+        if cls is None:
+            self._check(self.lib.gsim_set_peer_classes(self.h, None))
+            return
+        c = np.ascontiguousarray(cls, dtype=np.uint8)
+        if c.shape != (self.net.n,):
+            raise ValueError("peer classes: one byte per peer")
+        self._check(self.lib.gsim_set_peer_classes(self.h, _ptr(c)))
+
+    def net_report(self, edges=None):
+        """(mesh_rows, score_rows): per (topic, observer class) the mesh sizes,
+        links by the neighbour's class and fanout (MESH_ROW_DTYPE), and per
+        (observer class, subject class) the score snapshot's histogram over
+        `edges` (at most 15 ascending values; None: gsim.report.threshold_edges
+        of the engine's thresholds) with counts, min and max (SCORE_ROW_DTYPE),
+        reduced on the device (gsim_net_report; helpers: gsim.report)."""
+        from . import report
+        ed = report.threshold_edges(self.thresholds) if edges is None else edges
+        ed = np.ascontiguousarray(ed, dtype=np.float64).reshape(-1)
+        return _net_report_call(self, self.lib.gsim_net_report, self.h, ed)
+
     def read(self, f: int) -> np.ndarray:
         out = np.empty(self.field_shape(f), dtype=_FIELD_DTYPES[f])
         self._check(self.lib.gsim_read_field(self.h, f, _ptr(out), out.nbytes))
@@ -479,3 +506,15 @@ class Engine:
 
     def set_kernel_variant(self, which: int, variant: int):
         self._check(self.lib.gsim_set_kernel_variant(self.h, which, variant))
+
+
+def _net_report_call(eng, fn, handle, ed: np.ndarray):
+    """gsim_net_report / gsim_group_net_report: count, then fill."""
+    p = _ptr(ed) if len(ed) else None
+    nm, ns = ctypes.c_int64(0), ctypes.c_int64(0)
+    eng._check(fn(handle, p, len(ed), None, 0, ctypes.byref(nm), None, 0, ctypes.byref(ns)))
+    mesh = np.zeros(nm.value, dtype=Engine.MESH_ROW_DTYPE)
+    scores = np.zeros(ns.value, dtype=Engine.SCORE_ROW_DTYPE)
+    eng._check(fn(handle, p, len(ed), _ptr(mesh) if nm.value else None, nm.value, ctypes.byref(nm),
+                  _ptr(scores) if ns.value else None, ns.value, ctypes.byref(ns)))
+    return mesh, scores

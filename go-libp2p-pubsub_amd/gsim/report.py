@@ -6,7 +6,7 @@ d < REPORT_BINS - 1; the last bin holds every later one (its exact extent is
 max_latency)."""
 import numpy as np
 
-from ._abi import REPORT_BINS
+from ._abi import NET_CLASSES, NET_DEG_BINS, NET_OUT_BINS, REPORT_BINS
 
 
 def coverage(rep: np.ndarray) -> np.ndarray:
@@ -54,3 +54,51 @@ def cdf(rep: np.ndarray) -> np.ndarray:
     if denom == 0:
         return np.full(REPORT_BINS, np.nan)
     return np.cumsum(hist) / float(denom)
+
+
+# ---- network report (Engine.net_report: struct gsim_mesh_row / gsim_score_row) ----
+
+def threshold_edges(thresholds) -> np.ndarray:
+    """The default score histogram edges: the sorted distinct values of the
+    graylist, publish, gossip, accept-PX and opportunistic-graft thresholds
+    (a gsim.PeerScoreThresholds) and 0."""
+    vals = [thresholds.GraylistThreshold, thresholds.PublishThreshold, thresholds.GossipThreshold, 0.0,
+            thresholds.AcceptPXThreshold, thresholds.OpportunisticGraftThreshold]
+    return np.unique(np.asarray(vals, dtype=np.float64))
+
+
+def mesh_health(mesh_rows: np.ndarray, gossip_params) -> dict:
+    """Per mesh row the share of its members whose mesh is smaller than Dlo
+    ("below_dlo"), larger than Dhi ("above_dhi"), or holds fewer than Dout
+    outbound links ("below_dout"), from deg_hist / out_hist (a
+    gsim.GossipSubParams gives the bounds).  nan where a row has no members.
+    Bounds the histograms cannot resolve (Dlo or Dhi + 1 past the last degree
+    bin, Dout past the last outbound bin) raise ValueError."""
+    dlo, dhi, dout = int(gossip_params.Dlo), int(gossip_params.Dhi), int(gossip_params.Dout)
+    if dlo > NET_DEG_BINS - 1 or dhi + 1 > NET_DEG_BINS - 1 or dout > NET_OUT_BINS - 1:
+        raise ValueError("mesh bounds lie past the report's last exact bin")
+    deg = mesh_rows["deg_hist"].astype(np.int64).reshape(len(mesh_rows), NET_DEG_BINS)
+    out = mesh_rows["out_hist"].astype(np.int64).reshape(len(mesh_rows), NET_OUT_BINS)
+    members = mesh_rows["members"].astype(np.float64)
+
+    def share(count):
+        res = np.full(len(mesh_rows), np.nan)
+        np.divide(count.astype(np.float64), members, out=res, where=members > 0)
+        return res
+
+    return {"below_dlo": share(deg[:, :dlo].sum(axis=1)), "above_dhi": share(deg[:, dhi + 1:].sum(axis=1)),
+            "below_dout": share(out[:, :dout].sum(axis=1))}
+
+
+def class_share(mesh_rows: np.ndarray) -> np.ndarray:
+    """share[a, b]: the fraction of class a's mesh links, over every topic, that
+    point into class b ([C, C], C = the classes the rows name; a row of nan
+    for a class without mesh links)."""
+    C = int(mesh_rows["cls"].max()) + 1 if len(mesh_rows) else 0
+    links = np.zeros((C, NET_CLASSES), dtype=np.float64)
+    ml = mesh_rows["mesh_links"].astype(np.float64).reshape(len(mesh_rows), NET_CLASSES)
+    np.add.at(links, mesh_rows["cls"].astype(np.int64), ml)
+    tot = links.sum(axis=1, keepdims=True)
+    res = np.full((C, C), np.nan)
+    np.divide(links[:, :C], tot, out=res, where=tot > 0)
+    return res

@@ -434,6 +434,25 @@ class ShardedEngine:
             self._check(self.lib.gsim_group_msg_report(self.g, int(round_lo), hi, _ptr(out), n.value, ctypes.byref(n)))
         return out[:n.value]
 
+    def set_peer_classes(self, cls):
+        """Engine.set_peer_classes by global peer id (gsim_group_set_peer_classes)."""
+        if cls is None:
+            self._check(self.lib.gsim_group_set_peer_classes(self.g, None))
+            return
+        c = np.ascontiguousarray(cls, dtype=np.uint8)
+        if c.shape != (self.net.n,):
+            raise ValueError("peer classes: one byte per peer")
+        self._check(self.lib.gsim_group_set_peer_classes(self.g, _ptr(c)))
+
+    def net_report(self, edges=None):
+        """Engine.net_report over the shards of this process, merged
+        (gsim_group_net_report; one shard per process: the local shards' part)."""
+        from . import report
+        from .engine import _net_report_call
+        ed = report.threshold_edges(self.thresholds) if edges is None else edges
+        ed = np.ascontiguousarray(ed, dtype=np.float64).reshape(-1)
+        return _net_report_call(self, self.lib.gsim_group_net_report, self.g, ed)
+
     def msg_stats(self) -> list:
         out = np.zeros(4, dtype=np.int64)
         self._check(self.lib.gsim_group_msg_stats(self.g, _ptr(out)))

@@ -491,6 +491,62 @@ int gsim_gossip_stats(gsim_handle* h, int64_t* out4);
  * invalidMessageDeliveries, router mesh links, tracked edges}. */
 int gsim_census(gsim_handle* h, int64_t* out8);
 
+/* Network report: the meshes and the score snapshot as distributions by peer
+ * class, reduced on the device from the topic slot planes and the per-edge
+ * score state (no [T][E] view is built).
+ *
+ * gsim_set_peer_classes: one byte per peer, each < GSIM_NET_CLASSES; NULL:
+ * every peer is class 0 (the default).  C = 1 + the largest class set.  A
+ * value >= GSIM_NET_CLASSES: GSIM_EINVAL, the classes in force stay.  The
+ * classes key the report and nothing else; a new graph resets them.
+ *
+ * Defined on the ABI's edge-order views: for edge e of observer i (row
+ * owner) with neighbour j = col[e] and topic t,
+ *   mesh rows   one per (t, class of i), ordered (topic, cls).  The
+ *               GSIM_TF_MESH bits of GSIM_F_TFLAGS[t][e] count where i announces
+ *               t, the GSIM_TF_FANOUT bits where it does not; connection state is
+ *               not consulted.  sum(deg_hist) == sum(out_hist) == members and
+ *               sum(mesh_links) == the members' mesh sizes summed.
+ *   score rows  one per (class of i, class of j), ordered (obs_cls, subj_cls),
+ *               over GSIM_F_SCORE[e] (the snapshot) and GSIM_F_ESTATE[e].  hist
+ *               covers connected non-NaN scores s: bin 0 holds s < edges[0],
+ *               bin k edges[k-1] <= s < edges[k], bin n_edges s >=
+ *               edges[n_edges-1]; +-inf fall in the end bins and count for
+ *               min / max. */
+#define GSIM_NET_CLASSES    4
+#define GSIM_NET_DEG_BINS   32
+#define GSIM_NET_OUT_BINS   8
+#define GSIM_NET_SCORE_BINS 16
+struct gsim_mesh_row {
+    uint32_t topic, cls;
+    uint32_t members;                /* peers of cls announcing topic (sub bit)                         */
+    uint32_t max_degree;             /* largest mesh size among them, exact                             */
+    uint32_t fanout_peers;           /* peers of cls NOT announcing topic whose GSIM_F_FANOUT_TOPICS bit is set */
+    uint32_t _pad;
+    uint64_t mesh_links[GSIM_NET_CLASSES]; /* members' GSIM_TF_MESH edges, by the neighbour's class     */
+    uint64_t outbound_links;         /* of those, edges with outbound = 1                               */
+    uint64_t fanout_links;           /* GSIM_TF_FANOUT edges of the non-announcing peers of cls         */
+    uint32_t deg_hist[GSIM_NET_DEG_BINS];  /* members by mesh size d < 31; [31]: >= 31                  */
+    uint32_t out_hist[GSIM_NET_OUT_BINS];  /* members by outbound mesh links o < 7; [7]: >= 7           */
+};  /* 232 bytes */
+struct gsim_score_row {
+    uint32_t obs_cls, subj_cls;
+    uint64_t connected;              /* edges with GSIM_ES_CONNECTED                                    */
+    uint64_t retained;               /* GSIM_ES_TRACKED without GSIM_ES_CONNECTED                       */
+    uint64_t nan;                    /* connected edges whose snapshot score is NaN                     */
+    double   min, max;               /* over connected non-NaN edges; +inf / -inf when there are none   */
+    uint64_t hist[GSIM_NET_SCORE_BINS];
+};  /* 176 bytes */
+int gsim_set_peer_classes(gsim_handle* h, const uint8_t* cls);
+/* *n_mesh = T * C and *n_scores = C * C are always set.  A NULL array or a
+ * cap of 0 skips that half (both: the call only counts); a cap that is too
+ * small: GSIM_ERANGE, nothing written.  n_edges in 0..15, edges strictly
+ * ascending without NaN, else GSIM_EINVAL.  GSIM_ESTATE before
+ * gsim_load_graph.  Changes no state; synchronizes. */
+int gsim_net_report(gsim_handle* h, const double* edges, int32_t n_edges,
+                    struct gsim_mesh_row* mesh, int64_t mesh_cap, int64_t* n_mesh,
+                    struct gsim_score_row* scores, int64_t score_cap, int64_t* n_scores);
+
 /* ---- trace export (pb/trace.proto, trace.go) ------ */
 /* The events the routers [peer_lo, peer_hi) hand their tracer
  * (pubsubTracer, trace.go:70-530), one record each, in the order of
@@ -837,6 +893,15 @@ int gsim_group_census(gsim_group* g, int64_t* out8);
  * shard. */
 int gsim_group_msg_report(gsim_group* g, int64_t round_lo, int64_t round_hi,
                           struct gsim_msg_report* out, int64_t cap, int64_t* n);
+/* gsim_set_peer_classes / gsim_net_report over a sharded network: classes by
+ * global peer id (ghosts carry their owner's class); every local shard
+ * reports the observers it owns and the rows are merged: counts summed,
+ * max_degree the maximum, min / max of the scores.  With one shard per
+ * process the rows hold the local shards' part, as gsim_group_msg_report's. */
+int gsim_group_set_peer_classes(gsim_group* g, const uint8_t* cls);
+int gsim_group_net_report(gsim_group* g, const double* edges, int32_t n_edges,
+                          struct gsim_mesh_row* mesh, int64_t mesh_cap, int64_t* n_mesh,
+                          struct gsim_score_row* scores, int64_t score_cap, int64_t* n_scores);
 int gsim_group_synchronize(gsim_group* g);
 /* WithPeerScoreInspect over a sharded network (score.go:152-180, 448-500):
  * the whole network's view, filled from the rows this process's shards own
