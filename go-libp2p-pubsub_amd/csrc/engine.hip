@@ -1266,6 +1266,7 @@ int gsim_destroy(gsim_handle* h)
     free_deliver(h);
     trace_release(h);
     report_release(h);
+    peerreport_release(h);
     dfree(h->d_tp);
     dfree(h->d_flags);
     for (auto& ev : h->ev)

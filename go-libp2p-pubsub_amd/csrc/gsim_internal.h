@@ -446,6 +446,7 @@ struct TraceRef {
 struct Gater;   // the peer gater's state (gater.hip)
 struct Report;  // the propagation report's device scratch (report.hip)
 struct NetReport;  // the network report's peer classes and device scratch (netreport.hip)
+struct PeerReport; // the peer delivery report's device scratch (peerreport.hip)
 using MsgReport = struct ::gsim_msg_report;   // (the call gsim_msg_report hides the struct's name in C++)
 
 // The peer gater's device state as the delivery kernels see it (gater.hip;
@@ -585,6 +586,7 @@ struct gsim_handle {
     gsim::TraceRef trace;           // gsim_trace_config (trace.hip)
     gsim::Report* rp = nullptr;     // gsim_msg_report scratch (report.hip), allocated at the first call
     gsim::NetReport* nr = nullptr;  // gsim_set_peer_classes / gsim_net_report (netreport.hip); a new graph drops it
+    gsim::PeerReport* pr = nullptr; // gsim_peer_report scratch (peerreport.hip), allocated at the first call
 
     // owned peers / observer rows (all of them unless sharded)
     int64_t olo() const { return sh ? sh->own_lo : 0; }
@@ -738,6 +740,10 @@ void netreport_release(gsim_handle* h);
 // one class per local peer (nullptr: all 0); C > 0: the report's class count (a
 // shard takes the whole network's), C = 0: 1 + the largest class given
 int netreport_set_classes(gsim_handle* h, const uint8_t* cls, int C);
+// the classes in force: their count, and the device array of one byte per local
+// peer, ghosts included (nullptr: every peer is class 0)
+int netreport_classes(const gsim_handle* h, const uint8_t** d_cls);
+void peerreport_release(gsim_handle* h);  // peerreport.hip
 int64_t deliver_last_round_time(gsim_handle* h);   // time of the last round run (INT64_MAX: none yet)
 void trace_release(gsim_handle* h);   // trace.hip
 // round stages (deliver.hip; gsim_round runs them in order, a sharded group

@@ -410,6 +410,12 @@ int netreport_set_classes(gsim_handle* h, const uint8_t* cls, int C)
     return GSIM_OK;
 }
 
+int netreport_classes(const gsim_handle* h, const uint8_t** d_cls)
+{
+    *d_cls = h->nr ? h->nr->d_cls : nullptr;
+    return h->nr ? h->nr->C : 1;
+}
+
 extern "C" {
 
 int gsim_set_peer_classes(gsim_handle* h, const uint8_t* cls)

@@ -39,6 +39,7 @@
 #include "gsim.h"
 #include "gsim_internal.h"
 #include "netreport_merge.h"
+#include "peerreport_merge.h"
 #include "report_merge.h"
 #include "shard_layout.h"
 
@@ -2288,6 +2289,54 @@ int gsim_group_net_report(gsim_group* g, const double* edges, int32_t n_edges, s
     if (merge_net_reports(want_mesh ? mpp.data() : nullptr, want_scores ? spp.data() : nullptr, L, (size_t)nm, (size_t)ns,
                           want_mesh ? mesh : nullptr, want_scores ? scores : nullptr))
         return g->fail(GSIM_ESTATE, "the shards disagree about a report row's key");
+    return GSIM_OK;
+}
+
+// gsim_peer_report over the group: every local shard reports the peers it
+// owns, in its local ids; the per-peer rows land at the peers' global ids and
+// the class rows are merged on the host (peerreport_merge.cpp).  An owned
+// peer's committed cell names its first sender by a local id of the shard
+// (owned or ghost, peerreport.hip) and the shard's class array covers its
+// ghosts, so a first sender owned by another shard counts under its class.
+int gsim_group_peer_report(gsim_group* g, int64_t round_lo, int64_t round_hi, int64_t peer_lo, int64_t peer_hi,
+                           struct gsim_peer_row* peers, struct gsim_peer_class_row* classes, int64_t class_cap,
+                           int64_t* n_classes, int64_t* n_msgs)
+{
+    if (!g || !n_classes || !n_msgs || class_cap < 0) return GSIM_EINVAL;
+    *n_classes = *n_msgs = 0;
+    if (!g->msgs || g->hs.empty()) return g->fail(GSIM_ESTATE, "gsim_group_msgs_init not called");
+    if (peer_lo < 0 || peer_lo > peer_hi || peer_hi > g->N)
+        return g->fail(GSIM_EINVAL, "gsim_group_peer_report: the peer range must satisfy 0 <= peer_lo <= peer_hi <= N");
+    int64_t nc = 0, cnt = 0;
+    int rc = gsim_peer_report(g->hs[0], round_lo, round_hi, 0, 0, nullptr, nullptr, 0, &nc, &cnt);   // counts
+    *n_classes = nc;
+    *n_msgs = cnt;
+    if (rc) return g->take(g->hs[0], rc);
+    const bool want_cls = classes && class_cap > 0, want_peers = peers && peer_hi > peer_lo;
+    if (want_cls && class_cap < nc) return g->fail(GSIM_ERANGE, "gsim_group_peer_report: class row buffer too small");
+    if (!want_cls && !want_peers) return GSIM_OK;
+    const size_t L = g->hs.size();
+    std::vector<std::vector<gsim_peer_class_row>> parts(L);
+    std::vector<const gsim_peer_class_row*> pp;
+    std::vector<int64_t> got(L, 0);
+    for (size_t l = 0; l < L; ++l) {
+        gsim_handle* h = g->hs[l];
+        const ShardCtx* sc = h->sh;
+        const int k = g->ids[l];
+        // the part of the range this shard owns, in its local ids
+        const int64_t lo = std::max(peer_lo, g->bounds[(size_t)k]), hi = std::min(peer_hi, g->bounds[(size_t)k + 1]);
+        const bool rows = want_peers && lo < hi;
+        const int64_t llo = rows ? sc->own_lo + (lo - g->bounds[(size_t)k]) : 0, lhi = rows ? llo + (hi - lo) : 0;
+        if (want_cls) parts[l].resize((size_t)nc);
+        int64_t gc = 0;
+        rc = gsim_peer_report(h, round_lo, round_hi, llo, lhi, rows ? peers + (lo - peer_lo) : nullptr,
+                              want_cls ? parts[l].data() : nullptr, want_cls ? nc : 0, &gc, &got[l]);
+        if (rc) return g->take(h, rc);
+        if (gc != nc || got[l] != cnt) return g->fail(GSIM_ESTATE, "the shards disagree about the report's rows or messages");
+        pp.push_back(parts[l].data());
+    }
+    if (want_cls && merge_peer_reports(pp.data(), got.data(), L, (size_t)nc, classes))
+        return g->fail(GSIM_ESTATE, "the shards disagree about a class row's key or messages");
     return GSIM_OK;
 }
 

@@ -157,6 +157,30 @@ MESH_ROW_DTYPE = [("topic", "<u4"), ("cls", "<u4"), ("members", "<u4"), ("max_de
                   ("out_hist", "<u4", (NET_OUT_BINS,))]
 SCORE_ROW_DTYPE = [("obs_cls", "<u4"), ("subj_cls", "<u4"), ("connected", "<u8"), ("retained", "<u8"),
                    ("nan", "<u8"), ("min", "<f8"), ("max", "<f8"), ("hist", "<u8", (NET_SCORE_BINS,))]
+
+
+class CPeerRow(Structure):
+    """struct gsim_peer_row (48 bytes): one peer of the peer delivery report."""
+    _fields_ = [("expected", c_uint32), ("received", c_uint32), ("own", c_uint32), ("missed", c_uint32),
+                ("lat_max", c_uint32), ("_pad", c_uint32), ("lat_sum", c_uint64),
+                ("first_from", c_uint32 * NET_CLASSES)]
+
+
+class CPeerClassRow(Structure):
+    """struct gsim_peer_class_row (352 bytes): one (topic, receiver class) of the peer delivery report."""
+    _fields_ = [("topic", c_uint32), ("cls", c_uint32), ("peers", c_uint32), ("messages", c_uint32),
+                ("expected", c_uint64), ("received", c_uint64), ("own", c_uint64), ("missed", c_uint64),
+                ("lat_sum", c_uint64), ("lat_max", c_uint32), ("_pad", c_uint32),
+                ("first_from", c_uint64 * NET_CLASSES), ("hist", c_uint64 * REPORT_BINS)]
+
+
+# numpy views of struct gsim_peer_row / struct gsim_peer_class_row
+PEER_ROW_DTYPE = [("expected", "<u4"), ("received", "<u4"), ("own", "<u4"), ("missed", "<u4"), ("lat_max", "<u4"),
+                  ("_pad", "<u4"), ("lat_sum", "<u8"), ("first_from", "<u4", (NET_CLASSES,))]
+PEER_CLASS_ROW_DTYPE = [("topic", "<u4"), ("cls", "<u4"), ("peers", "<u4"), ("messages", "<u4"), ("expected", "<u8"),
+                        ("received", "<u8"), ("own", "<u8"), ("missed", "<u8"), ("lat_sum", "<u8"),
+                        ("lat_max", "<u4"), ("_pad", "<u4"), ("first_from", "<u8", (NET_CLASSES,)),
+                        ("hist", "<u8", (REPORT_BINS,))]
 MAX_VDELAY = 7          # gsim.h GSIM_MAX_VDELAY
 # gsim.h GSIM_VERDICT_*: the validation verdict of a message at every receiver
 VERDICT_ACCEPT, VERDICT_REJECT, VERDICT_IGNORE, VERDICT_THROTTLE, VERDICT_SIGNATURE = 0, 1, 2, 3, 4
@@ -300,6 +324,9 @@ SIGNATURES = [
     ("gsim_set_peer_classes", c_int32, [c_void_p, c_void_p]),
     ("gsim_net_report", c_int32, [c_void_p, c_void_p, c_int32, c_void_p, c_int64, POINTER(c_int64), c_void_p,
                                   c_int64, POINTER(c_int64)]),
+    ("gsim_peer_report", c_int32, [c_void_p, c_int64, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_int64,
+                                   POINTER(c_int64), POINTER(c_int64)]),
+    ("gsim_peer_report_launch", c_int32, [c_void_p, c_void_p]),
     ("gsim_set_peer_behaviour", c_int32, [c_void_p, c_void_p]),
     ("gsim_gossip_stats", c_int32, [c_void_p, c_void_p]),
     ("gsim_set_connections", c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int64]),
@@ -363,6 +390,8 @@ SIGNATURES = [
     ("gsim_group_set_peer_classes", c_int32, [c_void_p, c_void_p]),
     ("gsim_group_net_report", c_int32, [c_void_p, c_void_p, c_int32, c_void_p, c_int64, POINTER(c_int64), c_void_p,
                                         c_int64, POINTER(c_int64)]),
+    ("gsim_group_peer_report", c_int32, [c_void_p, c_int64, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_int64,
+                                         POINTER(c_int64), POINTER(c_int64)]),
     ("gsim_group_synchronize", c_int32, [c_void_p]),
     ("gsim_group_profile", c_int32, [c_void_p, c_int32]),
     ("gsim_group_profile_read", c_int32, [c_void_p, c_void_p, c_void_p, c_int32]),

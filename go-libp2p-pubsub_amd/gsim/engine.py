@@ -471,6 +471,27 @@ class Engine:
         ed = np.ascontiguousarray(ed, dtype=np.float64).reshape(-1)
         return _net_report_call(self, self.lib.gsim_net_report, self.h, ed)
 
+    # struct gsim_peer_row / struct gsim_peer_class_row
+    PEER_ROW_DTYPE = np.dtype(_abi.PEER_ROW_DTYPE)
+    PEER_CLASS_ROW_DTYPE = np.dtype(_abi.PEER_CLASS_ROW_DTYPE)
+
+    def peer_report(self, round_lo: int = 0, round_hi: int | None = None, peers=None, classes: bool = True):
+        """(peer_rows, class_rows) over the messages msg_report(round_lo,
+        round_hi) selects: per peer of `peers` (None: every peer; (lo, hi): that
+        range) the messages expected, received, missed, its latencies and its
+        first deliveries by the first sender's class (PEER_ROW_DTYPE), and per
+        (topic, class of the receiving peer) the same over every peer with a
+        latency histogram (PEER_CLASS_ROW_DTYPE; classes=False: an empty
+        array), reduced on the device from the seen-set cells
+        (gsim_peer_report; helpers: gsim.report)."""
+        return _peer_report_call(self, self.lib.gsim_peer_report, self.h, self.net.n, round_lo, round_hi, peers, classes)
+
+    def peer_report_launch(self) -> dict:
+        """How the last peer_report's reduction was launched (gsim_peer_report_launch)."""
+        out = np.zeros(3, dtype=np.int64)
+        self._check(self.lib.gsim_peer_report_launch(self.h, _ptr(out)))
+        return dict(zip(["waves", "parts", "messages"], (int(x) for x in out)))
+
     def read(self, f: int) -> np.ndarray:
         out = np.empty(self.field_shape(f), dtype=_FIELD_DTYPES[f])
         self._check(self.lib.gsim_read_field(self.h, f, _ptr(out), out.nbytes))
@@ -506,6 +527,20 @@ class Engine:
 
     def set_kernel_variant(self, which: int, variant: int):
         self._check(self.lib.gsim_set_kernel_variant(self.h, which, variant))
+
+
+def _peer_report_call(eng, fn, handle, n_peers, round_lo, round_hi, peers, classes):
+    """gsim_peer_report / gsim_group_peer_report: count the class rows, then fill."""
+    hi = (1 << 63) - 1 if round_hi is None else int(round_hi)
+    lo_p, hi_p = (0, int(n_peers)) if peers is None else (int(peers[0]), int(peers[1]))
+    nc, nm = ctypes.c_int64(0), ctypes.c_int64(0)
+    eng._check(fn(handle, int(round_lo), hi, lo_p, hi_p, None, None, 0, ctypes.byref(nc), ctypes.byref(nm)))
+    rows = np.zeros(max(hi_p - lo_p, 0), dtype=Engine.PEER_ROW_DTYPE)
+    cls = np.zeros(nc.value if classes else 0, dtype=Engine.PEER_CLASS_ROW_DTYPE)
+    if len(rows) or len(cls):
+        eng._check(fn(handle, int(round_lo), hi, lo_p, hi_p, _ptr(rows) if len(rows) else None,
+                      _ptr(cls) if len(cls) else None, len(cls), ctypes.byref(nc), ctypes.byref(nm)))
+    return rows, cls
 
 
 def _net_report_call(eng, fn, handle, ed: np.ndarray):

@@ -3,7 +3,8 @@ Engine.MSG_REPORT_DTYPE, struct gsim_msg_report): pure numpy, no device.
 
 hist[d] counts the peers a message reached d rounds after its publication,
 d < REPORT_BINS - 1; the last bin holds every later one (its exact extent is
-max_latency)."""
+max_latency).  Further down: the network report's and the peer delivery
+report's rows (Engine.net_report, Engine.peer_report)."""
 import numpy as np
 
 from ._abi import NET_CLASSES, NET_DEG_BINS, NET_OUT_BINS, REPORT_BINS
@@ -102,3 +103,43 @@ def class_share(mesh_rows: np.ndarray) -> np.ndarray:
     res = np.full((C, C), np.nan)
     np.divide(links[:, :C], tot, out=res, where=tot > 0)
     return res
+
+
+# ---- peer delivery report (Engine.peer_report: struct gsim_peer_row / gsim_peer_class_row) ----
+
+def delivery_ratio(peer_rows: np.ndarray) -> np.ndarray:
+    """Per row the share of the expected messages that arrived, (expected -
+    missed) / expected; nan where nothing was expected.  Works on per-peer rows
+    and on class rows alike."""
+    exp = peer_rows["expected"].astype(np.float64)
+    got = exp - peer_rows["missed"].astype(np.float64)
+    out = np.full(len(peer_rows), np.nan)
+    np.divide(got, exp, out=out, where=exp > 0)
+    return out
+
+
+def starved(peer_rows: np.ndarray, below: float) -> np.ndarray:
+    """Indices of the rows whose delivery_ratio lies under `below` (rows that
+    expected nothing are never starved)."""
+    ratio = delivery_ratio(peer_rows)
+    return np.nonzero(np.less(ratio, below, where=~np.isnan(ratio), out=np.zeros(len(ratio), dtype=bool)))[0]
+
+
+def source_share(rows: np.ndarray) -> np.ndarray:
+    """first_from normalised per row, [len(rows), NET_CLASSES]: the share of a
+    peer's (or a class row's) first deliveries that came from each sender
+    class, the eclipse measure; a row of nan where nothing was delivered by
+    another peer."""
+    ff = rows["first_from"].astype(np.float64).reshape(len(rows), NET_CLASSES)
+    tot = ff.sum(axis=1, keepdims=True)
+    out = np.full((len(rows), NET_CLASSES), np.nan)
+    np.divide(ff, tot, out=out, where=tot > 0)
+    return out
+
+
+def class_latency_quantile(class_rows: np.ndarray, q: float):
+    """latency_quantile over the class rows' histograms: per (topic, class) the
+    smallest latency d with at least q of its received deliveries at latency
+    <= d, and the overflow flag (True where the quantile falls in the last bin,
+    whose latency reads REPORT_BINS - 1, a lower bound)."""
+    return latency_quantile(class_rows, q)

@@ -453,6 +453,14 @@ class ShardedEngine:
         ed = np.ascontiguousarray(ed, dtype=np.float64).reshape(-1)
         return _net_report_call(self, self.lib.gsim_group_net_report, self.g, ed)
 
+    def peer_report(self, round_lo: int = 0, round_hi: int | None = None, peers=None, classes: bool = True):
+        """Engine.peer_report over the shards of this process: peer ranges and
+        per-peer rows in global ids, class rows merged (gsim_group_peer_report;
+        one shard per process: the local shards' part)."""
+        from .engine import _peer_report_call
+        return _peer_report_call(self, self.lib.gsim_group_peer_report, self.g, self.net.n, round_lo, round_hi, peers,
+                                 classes)
+
     def msg_stats(self) -> list:
         out = np.zeros(4, dtype=np.int64)
         self._check(self.lib.gsim_group_msg_stats(self.g, _ptr(out)))

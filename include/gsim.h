@@ -547,6 +547,71 @@ int gsim_net_report(gsim_handle* h, const double* edges, int32_t n_edges,
                     struct gsim_mesh_row* mesh, int64_t mesh_cap, int64_t* n_mesh,
                     struct gsim_score_row* scores, int64_t score_cap, int64_t* n_scores);
 
+/* Peer delivery report: the propagation report transposed.  The same seen-set
+ * cells, streamed once, reduced per peer and per (topic, class of the
+ * receiving peer) instead of per message: how many of the messages it
+ * subscribes to a peer received, how late, and who delivered them first (the
+ * victims' delivery ratio and the attacker class's share of their first
+ * deliveries are what eclipse, censorship and sybil studies read).  No
+ * [ring][N] view is built.
+ *
+ * Defined on the ABI's views: for peer p and selected message m (ring slot s,
+ * topic t, published in pub_round by origin),
+ *   selection     the messages of gsim_msg_report(round_lo, round_hi): pub_round
+ *                 in the window, never-published slots left out, a reused slot
+ *                 its current message only.
+ *   received      GSIM_F_SEEN[s][p] holds a round (a committed cell); the
+ *                 latency is that round minus pub_round, as gsim_msg_report's
+ *                 (with vdelay > 0 the round p's validation completes).
+ *   expected      p announces t now (its sub bit, gs.p.topics); missed: it does
+ *                 and the cell is not committed.  received + missed >= expected,
+ *                 equal unless p holds a cell of a topic it does not announce
+ *                 (a fanout publisher, a peer that left the topic).
+ *   first sender  the low word of the committed cell, the peer whose copy p saw
+ *                 first, counted by that peer's class (gsim_set_peer_classes;
+ *                 every peer class 0 by default).  The origin's own cell has no
+ *                 sender: it counts in `own` and in no first_from bin, so
+ *                 sum(first_from) == received - own in every row.
+ *   class rows    one per (t, class of p), ordered (topic, cls), over EVERY
+ *                 peer whatever the peer range; expected == peers * messages;
+ *                 sum(hist) == received. */
+struct gsim_peer_row {
+    uint32_t expected;   /* selected messages whose topic the peer announces now (sub bit)          */
+    uint32_t received;   /* selected messages with a committed cell of this peer, its own included  */
+    uint32_t own;        /* of those, the peer's own publications (origin == peer)                  */
+    uint32_t missed;     /* selected messages whose topic it announces and for which it has no committed cell */
+    uint32_t lat_max, _pad;
+    uint64_t lat_sum;    /* sum over received of first-seen round - pub_round (own: 0)              */
+    uint32_t first_from[GSIM_NET_CLASSES]; /* received - own, by the class of the first sender      */
+};  /* 48 bytes */
+struct gsim_peer_class_row {
+    uint32_t topic, cls;
+    uint32_t peers;      /* peers of cls announcing topic now                                      */
+    uint32_t messages;   /* selected messages of topic                                             */
+    uint64_t expected, received, own, missed, lat_sum;   /* expected == (u64)peers * messages      */
+    uint32_t lat_max, _pad;
+    uint64_t first_from[GSIM_NET_CLASSES];
+    uint64_t hist[GSIM_REPORT_BINS];   /* received by latency d < 31; [31]: >= 31; sum == received  */
+};  /* 352 bytes, first_from at offset 64, hist at 96 */
+/* peers == NULL skips the per-peer half; otherwise peer_hi - peer_lo rows are
+ * written for the peers [peer_lo, peer_hi); a range outside 0 <= peer_lo <=
+ * peer_hi <= N: GSIM_EINVAL.  *n_classes = T * C (as gsim_net_report's mesh
+ * rows) and *n_msgs, the number of selected messages, are always set.
+ * classes == NULL or class_cap == 0 skips the class rows; 0 < class_cap <
+ * T * C: GSIM_ERANGE, nothing written.  GSIM_ESTATE before gsim_msgs_init.
+ * Pending claims are committed first, so the call may follow any round.
+ * Changes no state; synchronizes; returns gsim_msg_stats's GSIM_ERANGE /
+ * GSIM_ESTATE (rows written) when the delivery error flags are set. */
+int gsim_peer_report(gsim_handle* h, int64_t round_lo, int64_t round_hi,
+                     int64_t peer_lo, int64_t peer_hi, struct gsim_peer_row* peers,
+                     struct gsim_peer_class_row* classes, int64_t class_cap,
+                     int64_t* n_classes, int64_t* n_msgs);
+/* Debug accessor: how the last gsim_peer_report that ran its reduction was
+ * launched, out3 = {waves of 64 peers, parts the selected slots were split
+ * into (1: every lane walks all of them and stores its row; > 1: the parts'
+ * partial sums meet in atomics on the rows), selected messages}. */
+int gsim_peer_report_launch(gsim_handle* h, int64_t* out3);
+
 /* ---- trace export (pb/trace.proto, trace.go) ------ */
 /* The events the routers [peer_lo, peer_hi) hand their tracer
  * (pubsubTracer, trace.go:70-530), one record each, in the order of
@@ -902,6 +967,20 @@ int gsim_group_set_peer_classes(gsim_group* g, const uint8_t* cls);
 int gsim_group_net_report(gsim_group* g, const double* edges, int32_t n_edges,
                           struct gsim_mesh_row* mesh, int64_t mesh_cap, int64_t* n_mesh,
                           struct gsim_score_row* scores, int64_t score_cap, int64_t* n_scores);
+/* gsim_peer_report over a sharded network: every local shard reports the
+ * peers it owns (a ghost's cell is never counted).  Peer ranges and per-peer
+ * rows are in global ids; the class rows are summed on the host (lat_max the
+ * maximum) and parts that disagree about a row's (topic, cls), its messages or
+ * the selected count are refused with GSIM_ESTATE.  A first sender owned by
+ * another shard is a ghost of the receiver's shard and carries its owner's
+ * class there (gsim_group_set_peer_classes).  With one shard per process the
+ * class rows hold the local shards' part and the per-peer rows of peers no
+ * local shard owns stay as the caller left them, as gsim_group_msg_report's
+ * rows and gsim_group_read_field's. */
+int gsim_group_peer_report(gsim_group* g, int64_t round_lo, int64_t round_hi,
+                           int64_t peer_lo, int64_t peer_hi, struct gsim_peer_row* peers,
+                           struct gsim_peer_class_row* classes, int64_t class_cap,
+                           int64_t* n_classes, int64_t* n_msgs);
 int gsim_group_synchronize(gsim_group* g);
 /* WithPeerScoreInspect over a sharded network (score.go:152-180, 448-500):
  * the whole network's view, filled from the rows this process's shards own
