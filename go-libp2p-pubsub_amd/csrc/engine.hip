@@ -1267,6 +1267,7 @@ int gsim_destroy(gsim_handle* h)
     trace_release(h);
     report_release(h);
     peerreport_release(h);
+    scorereport_release(h);
     dfree(h->d_tp);
     dfree(h->d_flags);
     for (auto& ev : h->ev)

@@ -211,6 +211,23 @@ __device__ __forceinline__ ctp_t const_tp(const gsim_topic_score_params* p)
     return (ctp_t)(p);
 }
 
+// f64 bits -> u64 that orders as the values do (-inf lowest, +inf highest; no
+// NaN comes here), and back: the reports' min / max are integer atomics on it
+// (netreport.hip, scorereport.hip).
+__host__ __device__ __forceinline__ unsigned long long f64_key(double s)
+{
+    unsigned long long u;
+    __builtin_memcpy(&u, &s, sizeof u);
+    return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
+}
+__host__ __device__ __forceinline__ double key_f64(unsigned long long k)
+{
+    const unsigned long long u = (k >> 63) ? (k & 0x7FFFFFFFFFFFFFFFull) : ~k;
+    double d;
+    __builtin_memcpy(&d, &u, sizeof d);
+    return d;
+}
+
 // How a field's ABI (edge-order) view maps onto device memory.
 enum FieldKind : int {
     FK_RAW = 0,      // same layout
@@ -447,6 +464,7 @@ struct Gater;   // the peer gater's state (gater.hip)
 struct Report;  // the propagation report's device scratch (report.hip)
 struct NetReport;  // the network report's peer classes and device scratch (netreport.hip)
 struct PeerReport; // the peer delivery report's device scratch (peerreport.hip)
+struct ScoreReport; // the score report's device scratch and what-if tables (scorereport.hip)
 using MsgReport = struct ::gsim_msg_report;   // (the call gsim_msg_report hides the struct's name in C++)
 
 // The peer gater's device state as the delivery kernels see it (gater.hip;
@@ -587,6 +605,7 @@ struct gsim_handle {
     gsim::Report* rp = nullptr;     // gsim_msg_report scratch (report.hip), allocated at the first call
     gsim::NetReport* nr = nullptr;  // gsim_set_peer_classes / gsim_net_report (netreport.hip); a new graph drops it
     gsim::PeerReport* pr = nullptr; // gsim_peer_report scratch (peerreport.hip), allocated at the first call
+    gsim::ScoreReport* sr = nullptr; // gsim_score_report scratch (scorereport.hip), allocated at the first call
 
     // owned peers / observer rows (all of them unless sharded)
     int64_t olo() const { return sh ? sh->own_lo : 0; }
@@ -744,6 +763,7 @@ int netreport_set_classes(gsim_handle* h, const uint8_t* cls, int C);
 // peer, ghosts included (nullptr: every peer is class 0)
 int netreport_classes(const gsim_handle* h, const uint8_t** d_cls);
 void peerreport_release(gsim_handle* h);  // peerreport.hip
+void scorereport_release(gsim_handle* h); // scorereport.hip
 int64_t deliver_last_round_time(gsim_handle* h);   // time of the last round run (INT64_MAX: none yet)
 void trace_release(gsim_handle* h);   // trace.hip
 // round stages (deliver.hip; gsim_round runs them in order, a sharded group

@@ -275,13 +275,7 @@ __global__ __launch_bounds__(kNetBlock) void k_net_mesh_hub(NetArgs a, const uin
     mesh_flush(s_acc, nacc, a.acc);
 }
 
-// f64 bits -> u64 that orders as the values do (-inf lowest, +inf highest; no NaN comes here)
-__device__ __forceinline__ unsigned long long f64_key(double s)
-{
-    const unsigned long long u = (unsigned long long)__double_as_longlong(s);
-    return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
-}
-
+// (min / max: f64_key / key_f64, gsim_internal.h)
 template <bool CLS>
 __global__ __launch_bounds__(kNetBlock) void k_net_score(NetArgs a, NetEdges ed)
 {
@@ -336,14 +330,6 @@ __global__ __launch_bounds__(kNetBlock) void k_net_score(NetArgs a, NetEdges ed)
         const unsigned long long v = s_mm[threadIdx.x];
         if (v) atomicMax(&a.acc[(threadIdx.x >> 1) * kSF + SF_MIN + (threadIdx.x & 1)], v);
     }
-}
-
-double key_f64(unsigned long long k)
-{
-    const unsigned long long u = (k >> 63) ? (k & 0x7FFFFFFFFFFFFFFFull) : ~k;
-    double d;
-    std::memcpy(&d, &u, sizeof d);
-    return d;
 }
 
 template <bool Dense, bool CLS>

@@ -39,6 +39,7 @@
 #include "gsim.h"
 #include "gsim_internal.h"
 #include "netreport_merge.h"
+#include "scorereport_merge.h"
 #include "peerreport_merge.h"
 #include "report_merge.h"
 #include "shard_layout.h"
@@ -2288,6 +2289,57 @@ int gsim_group_net_report(gsim_group* g, const double* edges, int32_t n_edges, s
     }
     if (merge_net_reports(want_mesh ? mpp.data() : nullptr, want_scores ? spp.data() : nullptr, L, (size_t)nm, (size_t)ns,
                           want_mesh ? mesh : nullptr, want_scores ? scores : nullptr))
+        return g->fail(GSIM_ESTATE, "the shards disagree about a report row's key");
+    return GSIM_OK;
+}
+
+// gsim_score_report over the group: every local shard reports the records of
+// the observers it owns under the same what-if parameters (a ghost subject
+// carries its class and its app-specific score); the rows are merged on the
+// host (scorereport_merge.cpp).
+int gsim_group_score_report(gsim_group* g, const struct gsim_score_what_if* what_if, const double* edges, int32_t n_edges,
+                            struct gsim_score_part_row* parts, int64_t part_cap, int64_t* n_parts,
+                            struct gsim_score_cause_row* causes, int64_t cause_cap, int64_t* n_causes,
+                            struct gsim_score_topic_row* topics, int64_t topic_cap, int64_t* n_topics)
+{
+    if (!g || !n_parts || !n_causes || !n_topics || part_cap < 0 || cause_cap < 0 || topic_cap < 0) return GSIM_EINVAL;
+    *n_parts = *n_causes = *n_topics = 0;
+    if (g->hs.empty()) return g->fail(GSIM_ESTATE, "the group holds no shard");
+    int64_t np = 0, nc = 0, nt = 0;
+    int rc = gsim_score_report(g->hs[0], what_if, edges, n_edges, nullptr, 0, &np, nullptr, 0, &nc, nullptr, 0,
+                               &nt);   // validates; counts
+    *n_parts = np;
+    *n_causes = nc;
+    *n_topics = nt;
+    if (rc) return g->take(g->hs[0], rc);
+    const bool want_parts = parts && part_cap > 0, want_causes = causes && cause_cap > 0, want_topics = topics && topic_cap > 0;
+    if ((want_parts && part_cap < np) || (want_causes && cause_cap < nc) || (want_topics && topic_cap < nt))
+        return g->fail(GSIM_ERANGE, "gsim_group_score_report: output buffer too small");
+    if (!want_parts && !want_causes && !want_topics) return GSIM_OK;
+    const size_t L = g->hs.size();
+    std::vector<std::vector<gsim_score_part_row>> pp(L);
+    std::vector<std::vector<gsim_score_cause_row>> cp(L);
+    std::vector<std::vector<gsim_score_topic_row>> tp(L);
+    std::vector<const gsim_score_part_row*> ppp;
+    std::vector<const gsim_score_cause_row*> cpp;
+    std::vector<const gsim_score_topic_row*> tpp;
+    for (size_t l = 0; l < L; ++l) {
+        if (want_parts) pp[l].resize((size_t)np);
+        if (want_causes) cp[l].resize((size_t)nc);
+        if (want_topics) tp[l].resize((size_t)nt);
+        int64_t gp = 0, gc = 0, gt = 0;
+        rc = gsim_score_report(g->hs[l], what_if, edges, n_edges, want_parts ? pp[l].data() : nullptr, want_parts ? np : 0,
+                               &gp, want_causes ? cp[l].data() : nullptr, want_causes ? nc : 0, &gc,
+                               want_topics ? tp[l].data() : nullptr, want_topics ? nt : 0, &gt);
+        if (rc) return g->take(g->hs[l], rc);
+        if (gp != np || gc != nc || gt != nt) return g->fail(GSIM_ESTATE, "the shards disagree about the report's rows");
+        ppp.push_back(pp[l].data());
+        cpp.push_back(cp[l].data());
+        tpp.push_back(tp[l].data());
+    }
+    if (merge_score_reports(want_parts ? ppp.data() : nullptr, want_causes ? cpp.data() : nullptr,
+                            want_topics ? tpp.data() : nullptr, L, (size_t)np, (size_t)nc, (size_t)nt,
+                            want_parts ? parts : nullptr, want_causes ? causes : nullptr, want_topics ? topics : nullptr))
         return g->fail(GSIM_ESTATE, "the shards disagree about a report row's key");
     return GSIM_OK;
 }

@@ -181,6 +181,47 @@ PEER_CLASS_ROW_DTYPE = [("topic", "<u4"), ("cls", "<u4"), ("peers", "<u4"), ("me
                         ("received", "<u8"), ("own", "<u8"), ("missed", "<u8"), ("lat_sum", "<u8"),
                         ("lat_max", "<u4"), ("_pad", "<u4"), ("first_from", "<u8", (NET_CLASSES,)),
                         ("hist", "<u8", (REPORT_BINS,))]
+
+# gsim.h GSIM_SR_*: the score report (gsim_score_report)
+SR_PARTS, SR_BINS, SR_CAUSES = 10, 33, 7
+SR_PART_NAMES = ("P1", "P2", "P3", "P3B", "P4", "TOPICS", "P5", "P6", "P7", "TOTAL")
+SR_CAUSE_NAMES = ("P3", "P3B", "P4", "P5", "P6", "P7", "NONE")
+(SR_P1, SR_P2, SR_P3, SR_P3B, SR_P4, SR_TOPICS, SR_P5, SR_P6, SR_P7, SR_TOTAL) = range(SR_PARTS)
+
+
+class CScorePartRow(Structure):
+    """struct gsim_score_part_row (304 bytes): one (observer class, subject class, part) of the score report."""
+    _fields_ = [("obs_cls", c_uint32), ("subj_cls", c_uint32), ("part", c_uint32), ("_pad", c_uint32),
+                ("nan", c_uint64), ("min", c_double), ("max", c_double), ("hist", c_uint64 * SR_BINS)]
+
+
+class CScoreCauseRow(Structure):
+    """struct gsim_score_cause_row (936 bytes): one (observer class, subject class): totals by bin and cause."""
+    _fields_ = [("obs_cls", c_uint32), ("subj_cls", c_uint32), ("connected", c_uint64), ("retained", c_uint64),
+                ("nan", c_uint64), ("capped", c_uint64), ("cause", (c_uint64 * SR_CAUSES) * NET_SCORE_BINS)]
+
+
+class CScoreTopicRow(Structure):
+    """struct gsim_score_topic_row (80 bytes): one (topic, observer class, subject class): flag counts."""
+    _fields_ = [("topic", c_uint32), ("obs_cls", c_uint32), ("subj_cls", c_uint32), ("_pad", c_uint32),
+                ("in_mesh", c_uint64), ("p1_capped", c_uint64), ("first_at_cap", c_uint64), ("active", c_uint64),
+                ("p3_deficit", c_uint64), ("p3b_nonzero", c_uint64), ("p4_nonzero", c_uint64), ("negative", c_uint64)]
+
+
+class CScoreWhatIf(Structure):
+    """struct gsim_score_what_if: the parameters a score report scores with instead of the engine's."""
+    _fields_ = [("peer", POINTER(CPeerScoreParams)), ("topics", POINTER(CTopicScoreParams)), ("n_topics", c_int32),
+                ("_pad", c_int32)]
+
+
+# numpy views of struct gsim_score_part_row / gsim_score_cause_row / gsim_score_topic_row
+SCORE_PART_ROW_DTYPE = [("obs_cls", "<u4"), ("subj_cls", "<u4"), ("part", "<u4"), ("_pad", "<u4"), ("nan", "<u8"),
+                        ("min", "<f8"), ("max", "<f8"), ("hist", "<u8", (SR_BINS,))]
+SCORE_CAUSE_ROW_DTYPE = [("obs_cls", "<u4"), ("subj_cls", "<u4"), ("connected", "<u8"), ("retained", "<u8"),
+                         ("nan", "<u8"), ("capped", "<u8"), ("cause", "<u8", (NET_SCORE_BINS, SR_CAUSES))]
+SCORE_TOPIC_ROW_DTYPE = [("topic", "<u4"), ("obs_cls", "<u4"), ("subj_cls", "<u4"), ("_pad", "<u4"),
+                         ("in_mesh", "<u8"), ("p1_capped", "<u8"), ("first_at_cap", "<u8"), ("active", "<u8"),
+                         ("p3_deficit", "<u8"), ("p3b_nonzero", "<u8"), ("p4_nonzero", "<u8"), ("negative", "<u8")]
 MAX_VDELAY = 7          # gsim.h GSIM_MAX_VDELAY
 # gsim.h GSIM_VERDICT_*: the validation verdict of a message at every receiver
 VERDICT_ACCEPT, VERDICT_REJECT, VERDICT_IGNORE, VERDICT_THROTTLE, VERDICT_SIGNATURE = 0, 1, 2, 3, 4
@@ -327,6 +368,9 @@ SIGNATURES = [
     ("gsim_peer_report", c_int32, [c_void_p, c_int64, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_int64,
                                    POINTER(c_int64), POINTER(c_int64)]),
     ("gsim_peer_report_launch", c_int32, [c_void_p, c_void_p]),
+    ("gsim_score_report", c_int32, [c_void_p, POINTER(CScoreWhatIf), c_void_p, c_int32, c_void_p, c_int64,
+                                    POINTER(c_int64), c_void_p, c_int64, POINTER(c_int64), c_void_p, c_int64,
+                                    POINTER(c_int64)]),
     ("gsim_set_peer_behaviour", c_int32, [c_void_p, c_void_p]),
     ("gsim_gossip_stats", c_int32, [c_void_p, c_void_p]),
     ("gsim_set_connections", c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int64]),
@@ -392,6 +436,9 @@ SIGNATURES = [
                                         c_int64, POINTER(c_int64)]),
     ("gsim_group_peer_report", c_int32, [c_void_p, c_int64, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_int64,
                                          POINTER(c_int64), POINTER(c_int64)]),
+    ("gsim_group_score_report", c_int32, [c_void_p, POINTER(CScoreWhatIf), c_void_p, c_int32, c_void_p, c_int64,
+                                          POINTER(c_int64), c_void_p, c_int64, POINTER(c_int64), c_void_p, c_int64,
+                                          POINTER(c_int64)]),
     ("gsim_group_synchronize", c_int32, [c_void_p]),
     ("gsim_group_profile", c_int32, [c_void_p, c_int32]),
     ("gsim_group_profile_read", c_int32, [c_void_p, c_void_p, c_void_p, c_int32]),

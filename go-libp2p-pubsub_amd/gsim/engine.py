@@ -14,7 +14,7 @@ from typing import List, Optional, Sequence
 import numpy as np
 
 from . import _abi
-from .params import GossipSubParams, PeerScoreParams, PeerScoreThresholds
+from .params import GossipSubParams, PeerScoreParams, PeerScoreThresholds, TopicScoreParams
 
 _FIELD_DTYPES = {
     _abi.F_FIRST: np.float64, _abi.F_MESHD: np.float64, _abi.F_FAIL: np.float64, _abi.F_INVALID: np.float64,
@@ -471,6 +471,29 @@ class Engine:
         ed = np.ascontiguousarray(ed, dtype=np.float64).reshape(-1)
         return _net_report_call(self, self.lib.gsim_net_report, self.h, ed)
 
+    # struct gsim_score_part_row / gsim_score_cause_row / gsim_score_topic_row
+    SCORE_PART_ROW_DTYPE = np.dtype(_abi.SCORE_PART_ROW_DTYPE)
+    SCORE_CAUSE_ROW_DTYPE = np.dtype(_abi.SCORE_CAUSE_ROW_DTYPE)
+    SCORE_TOPIC_ROW_DTYPE = np.dtype(_abi.SCORE_TOPIC_ROW_DTYPE)
+
+    def score_report(self, edges=None, params=None, topics=None):
+        """(part_rows, cause_rows, topic_rows): the live score of every record
+        decomposed into P1..P7 -- per (observer class, subject class, part) a
+        fixed signed-log histogram with min, max and NaN count
+        (SCORE_PART_ROW_DTYPE; bins: gsim.report.part_bin_bounds), per class
+        pair the totals by bin of `edges` (as net_report's) and dominant
+        negative part (SCORE_CAUSE_ROW_DTYPE), per (topic, class pair) the
+        flag counts (SCORE_TOPIC_ROW_DTYPE) -- reduced on the device from the
+        current counters.  What-if: `params`, a PeerScoreParams scored with
+        instead of the engine's (its .Topics give the topic table), and / or
+        `topics`, a {topic name: TopicScoreParams} laid over that table; the
+        engine's own parameters and state stay as they are
+        (gsim_score_report; helpers: gsim.report)."""
+        from . import report
+        ed = report.threshold_edges(self.thresholds) if edges is None else edges
+        ed = np.ascontiguousarray(ed, dtype=np.float64).reshape(-1)
+        return _score_report_call(self, self.lib.gsim_score_report, self.h, ed, params, topics)
+
     # struct gsim_peer_row / struct gsim_peer_class_row
     PEER_ROW_DTYPE = np.dtype(_abi.PEER_ROW_DTYPE)
     PEER_CLASS_ROW_DTYPE = np.dtype(_abi.PEER_CLASS_ROW_DTYPE)
@@ -541,6 +564,54 @@ def _peer_report_call(eng, fn, handle, n_peers, round_lo, round_hi, peers, class
         eng._check(fn(handle, int(round_lo), hi, lo_p, hi_p, _ptr(rows) if len(rows) else None,
                       _ptr(cls) if len(cls) else None, len(cls), ctypes.byref(nc), ctypes.byref(nm)))
     return rows, cls
+
+
+def _score_what_if(eng, params, topics):
+    """struct gsim_score_what_if of a PeerScoreParams and / or a topic overlay
+    (None when both are None), with the objects that must outlive the call."""
+    if params is None and topics is None:
+        return None, ()
+    w = _abi.CScoreWhatIf()
+    keep = []
+    if params is not None:
+        pc = params.to_c()
+        keep.append(pc)
+        w.peer = ctypes.pointer(pc)
+    if params is not None or topics:
+        table = dict((params if params is not None else eng.params).Topics)
+        for name, tp in (topics or {}).items():
+            if name not in eng.topic_index:
+                raise ValueError(f"score_report: unknown topic {name!r}")
+            table[name] = tp
+        arr = (_abi.CTopicScoreParams * max(1, len(eng.topics)))()
+        for i, name in enumerate(eng.topics):
+            arr[i] = table[name].to_c(True) if name in table else TopicScoreParams().to_c(False)
+        keep.append(arr)
+        w.topics = ctypes.cast(arr, ctypes.POINTER(_abi.CTopicScoreParams))
+        w.n_topics = max(1, len(eng.topics))
+    return w, keep
+
+
+def _score_report_call(eng, fn, handle, ed: np.ndarray, params, topics):
+    """gsim_score_report / gsim_group_score_report: count, then fill."""
+    w, keep = _score_what_if(eng, params, topics)
+    wp = ctypes.byref(w) if w is not None else None
+    p = _ptr(ed) if len(ed) else None
+    n = [ctypes.c_int64(0) for _ in range(3)]
+
+    def call(bufs):
+        args = []
+        for b, c in zip(bufs, n):
+            args += [_ptr(b) if b is not None and len(b) else None, len(b) if b is not None else 0, ctypes.byref(c)]
+        eng._check(fn(handle, wp, p, len(ed), *args))
+
+    call((None, None, None))
+    rows = (np.zeros(n[0].value, dtype=Engine.SCORE_PART_ROW_DTYPE),
+            np.zeros(n[1].value, dtype=Engine.SCORE_CAUSE_ROW_DTYPE),
+            np.zeros(n[2].value, dtype=Engine.SCORE_TOPIC_ROW_DTYPE))
+    call(rows)
+    del keep
+    return rows
 
 
 def _net_report_call(eng, fn, handle, ed: np.ndarray):

@@ -3,11 +3,13 @@ Engine.MSG_REPORT_DTYPE, struct gsim_msg_report): pure numpy, no device.
 
 hist[d] counts the peers a message reached d rounds after its publication,
 d < REPORT_BINS - 1; the last bin holds every later one (its exact extent is
-max_latency).  Further down: the network report's and the peer delivery
-report's rows (Engine.net_report, Engine.peer_report)."""
+max_latency).  Further down: the network report's, the peer delivery
+report's and the score report's rows (Engine.net_report, Engine.peer_report,
+Engine.score_report)."""
 import numpy as np
 
-from ._abi import NET_CLASSES, NET_DEG_BINS, NET_OUT_BINS, REPORT_BINS
+from ._abi import (NET_CLASSES, NET_DEG_BINS, NET_OUT_BINS, NET_SCORE_BINS, REPORT_BINS, SR_BINS, SR_CAUSES,
+                   SR_PARTS)
 
 
 def coverage(rep: np.ndarray) -> np.ndarray:
@@ -143,3 +145,74 @@ def class_latency_quantile(class_rows: np.ndarray, q: float):
     <= d, and the overflow flag (True where the quantile falls in the last bin,
     whose latency reads REPORT_BINS - 1, a lower bound)."""
     return latency_quantile(class_rows, q)
+
+
+# ---- score report (Engine.score_report: struct gsim_score_part_row / _cause_row / _topic_row) ----
+
+def part_bin_bounds() -> np.ndarray:
+    """[SR_BINS, 2]: (lo, hi) of each bin of a part row's hist.  The negative
+    bins 0..15 hold lo < x <= hi (bin 0: -inf .. -2^22, bin 15: -2^-6 .. 0,
+    zero excluded), bin 16 holds zero of either sign (lo = hi = 0), the
+    positive bins 17..32 hold lo <= x < hi (bin 17: 0 .. 2^-6, zero excluded;
+    bin 32: 2^22 .. +inf); in between the edges are the even powers 2^(2m - 8).
+    The infinities themselves fall in the end bins."""
+    pos = np.empty((16, 2))
+    for m in range(16):
+        pos[m] = (0.0 if m == 0 else 2.0 ** (2 * m - 8), np.inf if m == 15 else 2.0 ** (2 * m - 6))
+    out = np.zeros((SR_BINS, 2))
+    out[17:] = pos
+    out[:16] = -pos[::-1, ::-1]
+    return out
+
+
+def part_bin(x) -> np.ndarray:
+    """The hist bin of each value of x under gsim_score_report's rule (integer
+    arithmetic on the f64 bits); -1 for NaN, which a part row counts in `nan`."""
+    x = np.ascontiguousarray(x, dtype=np.float64)
+    u = x.view(np.uint64)
+    mag = u & np.uint64(0x7FFFFFFFFFFFFFFF)
+    k = (mag >> np.uint64(52)).astype(np.int64) - 1023
+    m = np.clip((k + 8) >> 1, 0, 15)
+    b = np.where((u >> np.uint64(63)) != 0, 15 - m, 17 + m)
+    b = np.where(mag == 0, 16, b)
+    return np.where(np.isnan(x), -1, b).astype(np.int64)
+
+
+def _class_count(rows) -> int:
+    return int(max(rows["obs_cls"].max(), rows["subj_cls"].max())) + 1 if len(rows) else 0
+
+
+def cause_below(cause_rows: np.ndarray, edges, threshold: float) -> np.ndarray:
+    """[C, C, SR_CAUSES]: per (observer class, subject class) the connected
+    records whose total lies under `threshold`, by dominant negative part
+    (_abi.SR_CAUSE_NAMES).  `edges` are the edges the report was taken with and
+    `threshold` must be one of them (only there does a bin boundary fall on
+    it), else ValueError."""
+    ed = np.asarray(edges, dtype=np.float64).reshape(-1)
+    hit = np.nonzero(ed == float(threshold))[0]
+    if len(hit) == 0:
+        raise ValueError("cause_below: the threshold is not one of the report's edges")
+    C = _class_count(cause_rows)
+    out = np.zeros((C, C, SR_CAUSES), dtype=np.int64)
+    cause = cause_rows["cause"].astype(np.int64).reshape(len(cause_rows), NET_SCORE_BINS, SR_CAUSES)
+    # bins 0 .. k hold the totals under edges[k]
+    np.add.at(out, (cause_rows["obs_cls"].astype(np.int64), cause_rows["subj_cls"].astype(np.int64)),
+              cause[:, :int(hit[0]) + 1].sum(axis=1))
+    return out
+
+
+def part_share_negative(part_rows: np.ndarray) -> np.ndarray:
+    """[C, C, SR_PARTS]: per (observer class, subject class) and part
+    (_abi.SR_PART_NAMES) the fraction of the connected records whose value of
+    the part is negative (NaN values count as connected, not as negative);
+    nan where a pair has no connected record."""
+    C = _class_count(part_rows)
+    hist = part_rows["hist"].astype(np.float64).reshape(len(part_rows), SR_BINS)
+    neg = np.zeros((C, C, SR_PARTS))
+    tot = np.zeros((C, C, SR_PARTS))
+    idx = (part_rows["obs_cls"].astype(np.int64), part_rows["subj_cls"].astype(np.int64), part_rows["part"].astype(np.int64))
+    np.add.at(neg, idx, hist[:, :16].sum(axis=1))
+    np.add.at(tot, idx, hist.sum(axis=1) + part_rows["nan"].astype(np.float64))
+    out = np.full((C, C, SR_PARTS), np.nan)
+    np.divide(neg, tot, out=out, where=tot > 0)
+    return out

@@ -453,6 +453,16 @@ class ShardedEngine:
         ed = np.ascontiguousarray(ed, dtype=np.float64).reshape(-1)
         return _net_report_call(self, self.lib.gsim_group_net_report, self.g, ed)
 
+    def score_report(self, edges=None, params=None, topics=None):
+        """Engine.score_report over the shards of this process, merged; the
+        what-if parameters go to every shard (gsim_group_score_report; one shard
+        per process: the local shards' part)."""
+        from . import report
+        from .engine import _score_report_call
+        ed = report.threshold_edges(self.thresholds) if edges is None else edges
+        ed = np.ascontiguousarray(ed, dtype=np.float64).reshape(-1)
+        return _score_report_call(self, self.lib.gsim_group_score_report, self.g, ed, params, topics)
+
     def peer_report(self, round_lo: int = 0, round_hi: int | None = None, peers=None, classes: bool = True):
         """Engine.peer_report over the shards of this process: peer ranges and
         per-peer rows in global ids, class rows merged (gsim_group_peer_report;

@@ -612,6 +612,114 @@ int gsim_peer_report(gsim_handle* h, int64_t round_lo, int64_t round_hi,
  * partial sums meet in atomics on the rows), selected messages}. */
 int gsim_peer_report_launch(gsim_handle* h, int64_t* out3);
 
+/* Score report: why a score is what it is.  The live score of every record
+ * decomposed into the reference's P1..P7 (score.go:265-342) as distributions
+ * per (observer class, subject class), reduced on the device in one read-only
+ * pass over the topic slot planes; optionally under other parameters than the
+ * engine's ("what if MeshMessageDeliveriesWeight were -0.5?").  No [T][E] view
+ * is built and no state changes.
+ *
+ * Defined on the ABI's edge-order views: for every edge e of observer i with
+ * subject j = col[e], on the CURRENT counters (not GSIM_F_SCORE, the snapshot
+ * of the last refresh):
+ *   counters    pending meshMessageDeliveries increments are applied with the
+ *               ENGINE's MeshMessageDeliveriesCap (they are state, not scoring);
+ *               meshTime is derived where the engine keeps it lazily; P6 is
+ *               taken as last derived (GSIM_F_P6): the report does not recompute
+ *               IP colocation.
+ *   records     a GSIM_ES_CONNECTED record counts everywhere; a GSIM_ES_TRACKED
+ *               record that is not connected counts in `retained` only; any other
+ *               record counts nowhere.  (A connected record without
+ *               GSIM_ES_TRACKED has no peerStats: every part of it is 0 and it
+ *               counts in no topic row, as its score is 0.)
+ *   per topic   with the parameters tp[t], pp (the engine's or the what-if
+ *               ones), per scored topic in ascending t:
+ *                 p1  = in_mesh ? min((double)(meshTime / quantum), cap) * w1 : 0
+ *                       (0 when the quantum is 0)
+ *                 p2  = first * w2
+ *                 p3  = (active && meshd < thr) ? ((thr - meshd) * (thr - meshd)) * w3 : 0
+ *                 p3b = fail * w3b
+ *                 p4  = (invalid * invalid) * w4
+ *                 ts  = ((((0 + p1) + p2) + p3) + p3b) + p4
+ *   parts       P1..P4: part_k = sum_t (p_k * TopicWeight_t), from 0.0 in
+ *               ascending t; TOPICS = sum_t ts * TopicWeight_t, then capped by
+ *               TopicScoreCap when that is > 0; P5 = p5[j] * AppSpecificWeight;
+ *               P6 = p6 * IPColocationFactorWeight; P7 = bp > thr7 ?
+ *               ((bp - thr7) * (bp - thr7)) * w7 : 0; TOTAL = ((TOPICS + P5) + P6)
+ *               + P7.  fp64, every operation rounded separately: TOTAL is bit for
+ *               bit the live score (what gsim_refresh_scores would store now,
+ *               decay aside).  The parts P1..P4 are sums of their own and need not
+ *               add up to TOPICS or TOTAL in the last bits.
+ *   hist        the bin of a part's value x, integer arithmetic on the f64 bits,
+ *               no caller-chosen edges (the parts span ten orders of magnitude):
+ *               zero of either sign: bin 16; otherwise k = floor(log2 |x|) (the
+ *               unbiased binary exponent; a denormal's is below -1022) and m =
+ *               clamp(floor((k + 8) / 2), 0, 15), +-inf: m = 15; x < 0: bin 15 - m,
+ *               x > 0: bin 17 + m.  So bin 0 is x <= -2^22, bin 15 is -2^-6 < x <
+ *               0, bin 17 is 0 < x < 2^-6, bin 32 is x >= 2^22, and in between bin
+ *               17 + m is 2^(2m-8) <= x < 2^(2m-6).  NaN counts in `nan`, not in
+ *               hist, min or max.
+ *   cause       the dominant negative part of a record: the smallest of (P3, P3B,
+ *               P4, P5, P6, P7) among those < 0 (NaN never qualifies, ties go to
+ *               the first in that order), NONE when none is negative.
+ *               cause[b][c] counts the connected records with a non-NaN TOTAL in
+ *               bin b of `edges` (gsim_net_report's rule) and cause c: its sum
+ *               over c is gsim_net_report's hist for the same edges while the
+ *               live total equals the snapshot (right after gsim_refresh_scores).
+ *   topic rows  flags of the connected tracked records per (topic, class pair);
+ *               the rows of a topic that is not scored are zero. */
+#define GSIM_SR_PARTS  10   /* P1 P2 P3 P3B P4 TOPICS P5 P6 P7 TOTAL, in this order */
+#define GSIM_SR_BINS   33
+#define GSIM_SR_CAUSES  7   /* P3 P3B P4 P5 P6 P7 NONE */
+enum {
+    GSIM_SR_P1 = 0, GSIM_SR_P2, GSIM_SR_P3, GSIM_SR_P3B, GSIM_SR_P4, GSIM_SR_TOPICS,
+    GSIM_SR_P5, GSIM_SR_P6, GSIM_SR_P7, GSIM_SR_TOTAL
+};
+struct gsim_score_part_row {          /* one per (obs_cls, subj_cls, part), in that order */
+    uint32_t obs_cls, subj_cls, part, _pad;
+    uint64_t nan;                     /* connected records whose value of this part is NaN */
+    double   min, max;                /* over connected non-NaN values; +inf / -inf when none */
+    uint64_t hist[GSIM_SR_BINS];      /* fixed signed-log bins, above */
+};  /* 304 bytes */
+struct gsim_score_cause_row {         /* one per (obs_cls, subj_cls) */
+    uint32_t obs_cls, subj_cls;
+    uint64_t connected, retained;     /* as gsim_score_row */
+    uint64_t nan;                     /* connected records whose TOTAL is NaN */
+    uint64_t capped;                  /* connected records whose topic sum exceeded TopicScoreCap (> 0) */
+    uint64_t cause[GSIM_NET_SCORE_BINS][GSIM_SR_CAUSES];
+                                      /* [bin of TOTAL on the caller's edges, gsim_net_report's rule]
+                                         [dominant negative part]; non-NaN totals only */
+};  /* 936 bytes */
+struct gsim_score_topic_row {         /* one per (topic, obs_cls, subj_cls); unscored topics: zeros */
+    uint32_t topic, obs_cls, subj_cls, _pad;
+    uint64_t in_mesh;                 /* GSIM_TF_IN_MESH */
+    uint64_t p1_capped;               /* in mesh and (double)(meshTime / quantum) > TimeInMeshCap */
+    uint64_t first_at_cap;            /* first >= FirstMessageDeliveriesCap */
+    uint64_t active;                  /* GSIM_TF_ACTIVE */
+    uint64_t p3_deficit;              /* active and meshd < MeshMessageDeliveriesThreshold */
+    uint64_t p3b_nonzero, p4_nonzero; /* fail != 0, invalid != 0 */
+    uint64_t negative;                /* ts * TopicWeight < 0 */
+};  /* 80 bytes */
+struct gsim_score_what_if {           /* NULL: the engine's own parameters */
+    const gsim_peer_score_params*  peer;    /* NULL: the engine's */
+    const gsim_topic_score_params* topics;  /* NULL: the engine's; else n_topics == T entries */
+    int32_t n_topics, _pad;
+};
+/* *n_parts = C * C * 10, *n_causes = C * C and *n_topics = T * C * C are always
+ * set (C: the classes of gsim_set_peer_classes).  A NULL array or a cap of 0
+ * skips that third (all three: the call only counts); a cap that is too small:
+ * GSIM_ERANGE, nothing written.  edges / n_edges as gsim_net_report's.  What-if
+ * parameters pass gsim_validate_peer_params / gsim_validate_topic_params and
+ * n_topics must equal T, else GSIM_EINVAL with the validator's text in
+ * gsim_last_error; they are used by this call only.  GSIM_ESTATE before
+ * gsim_load_graph.  Pending first deliveries are committed first (they are P2
+ * credits), so the call may follow any round.  Changes no state; synchronizes. */
+int gsim_score_report(gsim_handle* h, const struct gsim_score_what_if* what_if,
+                      const double* edges, int32_t n_edges,
+                      struct gsim_score_part_row*  parts,  int64_t part_cap,  int64_t* n_parts,
+                      struct gsim_score_cause_row* causes, int64_t cause_cap, int64_t* n_causes,
+                      struct gsim_score_topic_row* topics, int64_t topic_cap, int64_t* n_topics);
+
 /* ---- trace export (pb/trace.proto, trace.go) ------ */
 /* The events the routers [peer_lo, peer_hi) hand their tracer
  * (pubsubTracer, trace.go:70-530), one record each, in the order of
@@ -981,6 +1089,17 @@ int gsim_group_peer_report(gsim_group* g, int64_t round_lo, int64_t round_hi,
                            int64_t peer_lo, int64_t peer_hi, struct gsim_peer_row* peers,
                            struct gsim_peer_class_row* classes, int64_t class_cap,
                            int64_t* n_classes, int64_t* n_msgs);
+/* gsim_score_report over a sharded network: every local shard reports the
+ * records of the observers it owns (a ghost subject carries its class and its
+ * app-specific score), with the same what-if parameters; the rows are merged
+ * on the host: counts summed, min / max taken, parts that disagree about a
+ * row's key refused with GSIM_ESTATE.  With one shard per process the rows
+ * hold the local shards' part, as gsim_group_net_report's. */
+int gsim_group_score_report(gsim_group* g, const struct gsim_score_what_if* what_if,
+                            const double* edges, int32_t n_edges,
+                            struct gsim_score_part_row*  parts,  int64_t part_cap,  int64_t* n_parts,
+                            struct gsim_score_cause_row* causes, int64_t cause_cap, int64_t* n_causes,
+                            struct gsim_score_topic_row* topics, int64_t topic_cap, int64_t* n_topics);
 int gsim_group_synchronize(gsim_group* g);
 /* WithPeerScoreInspect over a sharded network (score.go:152-180, 448-500):
  * the whole network's view, filled from the rows this process's shards own
