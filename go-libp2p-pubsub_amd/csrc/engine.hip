@@ -740,6 +740,7 @@ void free_graph(gsim_handle* h)
     dfree(h->d_backoff); dfree(h->d_rstate); dfree(h->d_dstate); dfree(h->d_mcnt); dfree(h->d_pen);
     dfree(h->d_smask);
     netreport_release(h);        // peer classes are the old graph's
+    meshpaths_release(h);        // per-peer words sized to the old graph
     h->smask.clear();
     h->S = 0;
     h->bytes_allocated = 0;
@@ -1268,6 +1269,7 @@ int gsim_destroy(gsim_handle* h)
     report_release(h);
     peerreport_release(h);
     scorereport_release(h);
+    meshpaths_release(h);
     dfree(h->d_tp);
     dfree(h->d_flags);
     for (auto& ev : h->ev)

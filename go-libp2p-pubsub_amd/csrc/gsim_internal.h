@@ -465,6 +465,7 @@ struct Report;  // the propagation report's device scratch (report.hip)
 struct NetReport;  // the network report's peer classes and device scratch (netreport.hip)
 struct PeerReport; // the peer delivery report's device scratch (peerreport.hip)
 struct ScoreReport; // the score report's device scratch and what-if tables (scorereport.hip)
+struct MeshPaths;   // the mesh path report's per-peer words and counters (meshpaths.hip)
 using MsgReport = struct ::gsim_msg_report;   // (the call gsim_msg_report hides the struct's name in C++)
 
 // The peer gater's device state as the delivery kernels see it (gater.hip;
@@ -606,6 +607,7 @@ struct gsim_handle {
     gsim::NetReport* nr = nullptr;  // gsim_set_peer_classes / gsim_net_report (netreport.hip); a new graph drops it
     gsim::PeerReport* pr = nullptr; // gsim_peer_report scratch (peerreport.hip), allocated at the first call
     gsim::ScoreReport* sr = nullptr; // gsim_score_report scratch (scorereport.hip), allocated at the first call
+    gsim::MeshPaths* mp = nullptr;   // gsim_mesh_paths scratch (meshpaths.hip), allocated at the first call; a new graph drops it
 
     // owned peers / observer rows (all of them unless sharded)
     int64_t olo() const { return sh ? sh->own_lo : 0; }
@@ -764,6 +766,20 @@ int netreport_set_classes(gsim_handle* h, const uint8_t* cls, int C);
 int netreport_classes(const gsim_handle* h, const uint8_t** d_cls);
 void peerreport_release(gsim_handle* h);  // peerreport.hip
 void scorereport_release(gsim_handle* h); // scorereport.hip
+// meshpaths.hip: the mesh path report (gsim_mesh_paths) in steps, which
+// gsim_group_mesh_paths (shard.hip) interleaves with the ghosts' exchange.
+// Sources are local ids (0xFFFFFFFF: another shard's, no seed here).
+void meshpaths_release(gsim_handle* h);
+int meshpaths_begin(gsim_handle* h, int32_t topic, const uint32_t* src_local, int32_t n_sources, uint32_t blocked,
+                    bool per_peer);                                   // clears the words, seeds level 0
+int meshpaths_push(gsim_handle* h);                                   // cur -> nxt over the owned rows
+// reads the nxt words of the local peers outside [olo, ohi) into host[n] (the owned part is left alone); synchronizes
+int meshpaths_ghost_bits(gsim_handle* h, uint64_t* host);
+// nxt (| inc, a host array over the owned peers, or nullptr) -> seen, cur and the counters; *any: the sources whose frontier is not empty
+int meshpaths_fold(gsim_handle* h, int32_t level, const uint64_t* inc, uint64_t* any);
+// the rows (source / topic as given) and the per-peer arrays over the local peers ([n] each, or nullptr)
+int meshpaths_finish(gsim_handle* h, const uint32_t* sources, uint64_t truncated, struct gsim_mesh_path_row* rows,
+                     uint32_t* reach_count, uint32_t* hop_sum);
 int64_t deliver_last_round_time(gsim_handle* h);   // time of the last round run (INT64_MAX: none yet)
 void trace_release(gsim_handle* h);   // trace.hip
 // round stages (deliver.hip; gsim_round runs them in order, a sharded group

@@ -38,6 +38,7 @@
 
 #include "gsim.h"
 #include "gsim_internal.h"
+#include "meshpaths_merge.h"
 #include "netreport_merge.h"
 #include "scorereport_merge.h"
 #include "peerreport_merge.h"
@@ -2389,6 +2390,110 @@ int gsim_group_peer_report(gsim_group* g, int64_t round_lo, int64_t round_hi, in
     }
     if (want_cls && merge_peer_reports(pp.data(), got.data(), L, (size_t)nc, classes))
         return g->fail(GSIM_ESTATE, "the shards disagree about a class row's key or messages");
+    return GSIM_OK;
+}
+
+// gsim_mesh_paths over the group (meshpaths.hip's steps): every shard expands
+// the frontier of its owned peers over its own rows; between the push and the
+// fold of a level the bits that landed on ghosts are read from every shard,
+// translated to global ids (gid) and ORed into the owner's fold.  The rows are
+// summed on the host (meshpaths_merge.cpp); the per-peer arrays land at the
+// owned peers' global ids.
+int gsim_group_mesh_paths(gsim_group* g, int32_t topic, const uint32_t* sources, int32_t n_sources, uint32_t blocked,
+                          int32_t max_hops, struct gsim_mesh_path_row* rows, uint32_t* reach_count, uint32_t* hop_sum)
+{
+    if (!g || !sources || !rows) return GSIM_EINVAL;
+    if (g->hs.empty() || g->N == 0) return g->fail(GSIM_ESTATE, "no graph loaded (call gsim_group_load_graph first)");
+    if ((int)g->hs.size() != g->K)
+        return g->fail(GSIM_ESTATE, "gsim_group_mesh_paths: the group's shards span processes (the frontier exchange "
+                                    "needs every shard in this process)");
+    if (n_sources < 1 || n_sources > GSIM_PATH_SOURCES) return g->fail(GSIM_EINVAL, "gsim_group_mesh_paths: n_sources must lie in 1..64");
+    if (topic < 0 || topic >= g->hs[0]->t) return g->fail(GSIM_EINVAL, "gsim_group_mesh_paths: topic out of range");
+    for (int k = 0; k < n_sources; ++k)
+        if ((int64_t)sources[k] >= g->N) return g->fail(GSIM_EINVAL, "gsim_group_mesh_paths: a source is not a peer");
+    const uint8_t* d_cls;
+    if (blocked >> netreport_classes(g->hs[0], &d_cls))
+        return g->fail(GSIM_EINVAL, "gsim_group_mesh_paths: a blocked bit is at or above the class count");
+    if (max_hops < 0) return g->fail(GSIM_EINVAL, "gsim_group_mesh_paths: max_hops must not be negative");
+    const size_t L = g->hs.size();
+    std::vector<size_t> local_of((size_t)g->K, 0);                 // shard id -> index in hs
+    for (size_t l = 0; l < L; ++l) local_of[(size_t)g->ids[l]] = l;
+    auto owner_of = [&](int64_t p) {                               // the shard that owns global peer p
+        return (size_t)(std::upper_bound(g->bounds.begin(), g->bounds.end(), p) - g->bounds.begin() - 1);
+    };
+    const bool per_peer = reach_count || hop_sum;
+    int rc;
+    for (size_t l = 0; l < L; ++l) {
+        const ShardCtx* sc = g->hs[l]->sh;
+        uint32_t src[GSIM_PATH_SOURCES];
+        for (int k = 0; k < n_sources; ++k) {
+            const size_t o = owner_of(sources[k]);
+            src[k] = (int)o == g->ids[l] ? (uint32_t)(sc->own_lo + ((int64_t)sources[k] - g->bounds[o])) : 0xFFFFFFFFu;
+        }
+        if ((rc = meshpaths_begin(g->hs[l], topic, src, n_sources, blocked, per_peer))) return g->take(g->hs[l], rc);
+    }
+    std::vector<std::vector<uint64_t>> inc(L);
+    std::vector<uint8_t> dirty(L, 0);
+    std::vector<uint64_t> ghost;
+    auto fold_all = [&](int32_t level, uint64_t* any) {
+        *any = 0;
+        for (size_t l = 0; l < L; ++l) {
+            uint64_t w = 0;
+            const int r = meshpaths_fold(g->hs[l], level, dirty[l] ? inc[l].data() : nullptr, &w);
+            if (r) return g->take(g->hs[l], r);
+            *any |= w;
+        }
+        return (int)GSIM_OK;
+    };
+    uint64_t any = 0, truncated = 0;
+    int32_t level = 0;
+    if ((rc = fold_all(0, &any))) return rc;
+    while (any) {
+        if (max_hops > 0 && level == max_hops) { truncated = any; break; }
+        for (size_t l = 0; l < L; ++l)
+            if ((rc = meshpaths_push(g->hs[l]))) return g->take(g->hs[l], rc);
+        for (size_t l = 0; l < L; ++l) {
+            const ShardCtx* sc = g->hs[l]->sh;
+            inc[l].assign((size_t)(sc->own_hi - sc->own_lo), 0ull);
+            dirty[l] = 0;
+        }
+        for (size_t l = 0; l < L; ++l) {                           // the ghosts' bits to their owners
+            gsim_handle* h = g->hs[l];
+            const ShardCtx* sc = h->sh;
+            if (sc->own_hi - sc->own_lo == h->n) continue;         // no ghosts
+            ghost.assign((size_t)h->n, 0ull);
+            if ((rc = meshpaths_ghost_bits(h, ghost.data()))) return g->take(h, rc);
+            for (int64_t x = 0; x < h->n; ++x) {
+                if (x >= sc->own_lo && x < sc->own_hi) continue;
+                const uint64_t w = ghost[(size_t)x];
+                if (!w) continue;
+                const int64_t p = g->gid[l][(size_t)x];
+                const size_t o = owner_of(p), lo = local_of[o];
+                inc[lo][(size_t)(p - g->bounds[o])] |= w;
+                dirty[lo] = 1;
+            }
+        }
+        ++level;
+        if ((rc = fold_all(level, &any))) return rc;
+    }
+    std::vector<std::vector<gsim_mesh_path_row>> parts(L);
+    std::vector<const gsim_mesh_path_row*> pp;
+    std::vector<uint32_t> lrc, lhs;
+    for (size_t l = 0; l < L; ++l) {
+        gsim_handle* h = g->hs[l];
+        const ShardCtx* sc = h->sh;
+        parts[l].resize((size_t)n_sources);
+        if (per_peer) { lrc.assign((size_t)h->n, 0u); lhs.assign((size_t)h->n, 0u); }
+        if ((rc = meshpaths_finish(h, sources, truncated, parts[l].data(), per_peer ? lrc.data() : nullptr,
+                                   per_peer ? lhs.data() : nullptr)))
+            return g->take(h, rc);
+        pp.push_back(parts[l].data());
+        const size_t g0 = (size_t)g->bounds[(size_t)g->ids[l]], cnt = (size_t)(sc->own_hi - sc->own_lo);
+        if (reach_count && cnt) std::memcpy(reach_count + g0, lrc.data() + sc->own_lo, sizeof(uint32_t) * cnt);
+        if (hop_sum && cnt) std::memcpy(hop_sum + g0, lhs.data() + sc->own_lo, sizeof(uint32_t) * cnt);
+    }
+    if (merge_mesh_paths(pp.data(), L, (size_t)n_sources, rows))
+        return g->fail(GSIM_ESTATE, "the shards disagree about a path row's source, topic or subscribers");
     return GSIM_OK;
 }
 

@@ -182,6 +182,22 @@ PEER_CLASS_ROW_DTYPE = [("topic", "<u4"), ("cls", "<u4"), ("peers", "<u4"), ("me
                         ("lat_max", "<u4"), ("_pad", "<u4"), ("first_from", "<u8", (NET_CLASSES,)),
                         ("hist", "<u8", (REPORT_BINS,))]
 
+# gsim.h GSIM_PATH_SOURCES: the mesh path report (gsim_mesh_paths)
+PATH_SOURCES = 64
+
+
+class CMeshPathRow(Structure):
+    """struct gsim_mesh_path_row (184 bytes): one source of the mesh path report."""
+    _fields_ = [("source", c_uint32), ("topic", c_uint32), ("reached", c_uint32), ("subscribers", c_uint32),
+                ("max_hops", c_uint32), ("truncated", c_uint32), ("reached_cls", c_uint32 * NET_CLASSES),
+                ("members_cls", c_uint32 * NET_CLASSES), ("hist", c_uint32 * REPORT_BINS)]
+
+
+# numpy view of struct gsim_mesh_path_row
+MESH_PATH_ROW_DTYPE = [("source", "<u4"), ("topic", "<u4"), ("reached", "<u4"), ("subscribers", "<u4"),
+                       ("max_hops", "<u4"), ("truncated", "<u4"), ("reached_cls", "<u4", (NET_CLASSES,)),
+                       ("members_cls", "<u4", (NET_CLASSES,)), ("hist", "<u4", (REPORT_BINS,))]
+
 # gsim.h GSIM_SR_*: the score report (gsim_score_report)
 SR_PARTS, SR_BINS, SR_CAUSES = 10, 33, 7
 SR_PART_NAMES = ("P1", "P2", "P3", "P3B", "P4", "TOPICS", "P5", "P6", "P7", "TOTAL")
@@ -371,6 +387,8 @@ SIGNATURES = [
     ("gsim_score_report", c_int32, [c_void_p, POINTER(CScoreWhatIf), c_void_p, c_int32, c_void_p, c_int64,
                                     POINTER(c_int64), c_void_p, c_int64, POINTER(c_int64), c_void_p, c_int64,
                                     POINTER(c_int64)]),
+    ("gsim_mesh_paths", c_int32, [c_void_p, c_int32, c_void_p, c_int32, c_uint32, c_int32, c_void_p, c_void_p,
+                                  c_void_p]),
     ("gsim_set_peer_behaviour", c_int32, [c_void_p, c_void_p]),
     ("gsim_gossip_stats", c_int32, [c_void_p, c_void_p]),
     ("gsim_set_connections", c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int64]),
@@ -439,6 +457,8 @@ SIGNATURES = [
     ("gsim_group_score_report", c_int32, [c_void_p, POINTER(CScoreWhatIf), c_void_p, c_int32, c_void_p, c_int64,
                                           POINTER(c_int64), c_void_p, c_int64, POINTER(c_int64), c_void_p, c_int64,
                                           POINTER(c_int64)]),
+    ("gsim_group_mesh_paths", c_int32, [c_void_p, c_int32, c_void_p, c_int32, c_uint32, c_int32, c_void_p, c_void_p,
+                                        c_void_p]),
     ("gsim_group_synchronize", c_int32, [c_void_p]),
     ("gsim_group_profile", c_int32, [c_void_p, c_int32]),
     ("gsim_group_profile_read", c_int32, [c_void_p, c_void_p, c_void_p, c_int32]),

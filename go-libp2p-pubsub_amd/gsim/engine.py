@@ -509,6 +509,24 @@ class Engine:
         (gsim_peer_report; helpers: gsim.report)."""
         return _peer_report_call(self, self.lib.gsim_peer_report, self.h, self.net.n, round_lo, round_hi, peers, classes)
 
+    # struct gsim_mesh_path_row
+    MESH_PATH_ROW_DTYPE = np.dtype(_abi.MESH_PATH_ROW_DTYPE)
+
+    def mesh_paths(self, topic: int, sources, blocked=(), max_hops: int = 0, per_peer: bool = False):
+        """Hop distances over the mesh of `topic` from every peer of `sources`
+        (a source outside the topic expands once over its fanout), one
+        MESH_PATH_ROW_DTYPE row per source in the given order: reached,
+        subscribers, the exact largest distance, a distance histogram and the
+        reach by peer class.  `blocked`: the peer classes that are reached but
+        do not relay (a read-only what-if; a source still forwards its own
+        publication); `max_hops` > 0 stops after that many levels.
+        per_peer=True: (rows, reach_count, hop_sum), per peer the number of
+        sources that reach it and the sum of its distances.  More than 64
+        sources run in batches of 64.  A traversal on the device
+        (gsim_mesh_paths; helpers: gsim.report)."""
+        return _mesh_paths_call(self, self.lib.gsim_mesh_paths, self.h, self.net.n, topic, sources, blocked, max_hops,
+                                per_peer)
+
     def peer_report_launch(self) -> dict:
         """How the last peer_report's reduction was launched (gsim_peer_report_launch)."""
         out = np.zeros(3, dtype=np.int64)
@@ -550,6 +568,32 @@ class Engine:
 
     def set_kernel_variant(self, which: int, variant: int):
         self._check(self.lib.gsim_set_kernel_variant(self.h, which, variant))
+
+
+def _mesh_paths_call(eng, fn, handle, n_peers, topic, sources, blocked, max_hops, per_peer):
+    """gsim_mesh_paths / gsim_group_mesh_paths in batches of _abi.PATH_SOURCES:
+    rows concatenated, the per-peer arrays summed."""
+    src = np.ascontiguousarray(sources, dtype=np.uint32).reshape(-1)
+    mask = 0
+    for c in ([blocked] if np.isscalar(blocked) else blocked):
+        if not 0 <= int(c) < 32:
+            raise ValueError("mesh_paths: a blocked class must lie in 0..31")
+        mask |= 1 << int(c)
+    rows = np.zeros(len(src), dtype=Engine.MESH_PATH_ROW_DTYPE)
+    reach = np.zeros(n_peers, dtype=np.uint32)
+    hops = np.zeros(n_peers, dtype=np.uint32)
+    for lo in range(0, len(src), _abi.PATH_SOURCES):
+        part = np.ascontiguousarray(src[lo:lo + _abi.PATH_SOURCES])
+        out = np.zeros(len(part), dtype=Engine.MESH_PATH_ROW_DTYPE)
+        rc = np.zeros(n_peers, dtype=np.uint32) if per_peer else None
+        hs = np.zeros(n_peers, dtype=np.uint32) if per_peer else None
+        eng._check(fn(handle, int(topic), _ptr(part), len(part), mask, int(max_hops), _ptr(out),
+                      _ptr(rc) if per_peer else None, _ptr(hs) if per_peer else None))
+        rows[lo:lo + len(part)] = out
+        if per_peer:
+            reach += rc
+            hops += hs
+    return (rows, reach, hops) if per_peer else rows
 
 
 def _peer_report_call(eng, fn, handle, n_peers, round_lo, round_hi, peers, classes):

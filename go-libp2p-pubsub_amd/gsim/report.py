@@ -4,7 +4,8 @@ Engine.MSG_REPORT_DTYPE, struct gsim_msg_report): pure numpy, no device.
 hist[d] counts the peers a message reached d rounds after its publication,
 d < REPORT_BINS - 1; the last bin holds every later one (its exact extent is
 max_latency).  Further down: the network report's, the peer delivery
-report's and the score report's rows (Engine.net_report, Engine.peer_report,
+report's, the mesh path report's and the score report's rows
+(Engine.net_report, Engine.peer_report, Engine.mesh_paths,
 Engine.score_report)."""
 import numpy as np
 
@@ -145,6 +146,53 @@ def class_latency_quantile(class_rows: np.ndarray, q: float):
     <= d, and the overflow flag (True where the quantile falls in the last bin,
     whose latency reads REPORT_BINS - 1, a lower bound)."""
     return latency_quantile(class_rows, q)
+
+
+# ---- mesh path report (Engine.mesh_paths: struct gsim_mesh_path_row) ----
+
+def hop_quantile(rows: np.ndarray, q: float) -> np.ndarray:
+    """Per source the smallest distance d with at least q of its reached peers
+    within d hops, read from hist (a source that reaches nobody reads 0).  A
+    quantile that falls in the last bin, which holds every distance >=
+    REPORT_BINS - 1, cannot be answered from the bins: ValueError (as
+    mesh_health refuses bounds past its last exact bin)."""
+    if not 0.0 <= q <= 1.0:
+        raise ValueError("q must lie in [0, 1]")
+    hops, overflow = latency_quantile(rows, q)
+    if overflow.any():
+        raise ValueError("hop_quantile: the quantile lies in the overflow bin (distances >= %d)" % (REPORT_BINS - 1))
+    return hops
+
+
+def reach_ratio(rows: np.ndarray) -> np.ndarray:
+    """reached / subscribers per source (nan where nobody announces the topic)."""
+    return coverage(rows)
+
+
+def censored_share(rows_plain: np.ndarray, rows_blocked: np.ndarray, blocked=()) -> np.ndarray:
+    """Per source the share of the peers outside the classes `blocked` that the
+    plain traversal reaches and the one with those classes blocked does not:
+    1 - reached_cls(blocked run) / reached_cls(plain run), both summed over the
+    other classes.  The two arrays hold the same sources in the same order
+    (ValueError otherwise); nan where the plain run reaches no such peer."""
+    if len(rows_plain) != len(rows_blocked) or (rows_plain["source"] != rows_blocked["source"]).any() \
+            or (rows_plain["topic"] != rows_blocked["topic"]).any():
+        raise ValueError("censored_share: the two runs must hold the same sources and topic, in the same order")
+    keep = np.ones(NET_CLASSES, dtype=bool)
+    for c in ([blocked] if np.isscalar(blocked) else blocked):
+        keep[int(c)] = False
+    plain = rows_plain["reached_cls"].astype(np.float64).reshape(len(rows_plain), NET_CLASSES)[:, keep].sum(axis=1)
+    cut = rows_blocked["reached_cls"].astype(np.float64).reshape(len(rows_blocked), NET_CLASSES)[:, keep].sum(axis=1)
+    out = np.full(len(rows_plain), np.nan)
+    np.divide(plain - cut, plain, out=out, where=plain > 0)
+    return out
+
+
+def unreachable(reach_count: np.ndarray, n_sources: int) -> np.ndarray:
+    """Indices of the peers that fewer than n_sources sources reach (per-peer
+    reach_count of Engine.mesh_paths(..., per_peer=True)); peers outside the
+    topic are among them, no source reaches those."""
+    return np.nonzero(np.asarray(reach_count).astype(np.int64) < int(n_sources))[0]
 
 
 # ---- score report (Engine.score_report: struct gsim_score_part_row / _cause_row / _topic_row) ----

@@ -471,6 +471,15 @@ class ShardedEngine:
         return _peer_report_call(self, self.lib.gsim_group_peer_report, self.g, self.net.n, round_lo, round_hi, peers,
                                  classes)
 
+    def mesh_paths(self, topic: int, sources, blocked=(), max_hops: int = 0, per_peer: bool = False):
+        """Engine.mesh_paths over the shards of this process: sources and the
+        per-peer arrays in global ids, the frontiers exchanged between the
+        levels, the rows summed (gsim_group_mesh_paths; a group whose shards
+        span processes: GSIM_ESTATE)."""
+        from .engine import _mesh_paths_call
+        return _mesh_paths_call(self, self.lib.gsim_group_mesh_paths, self.g, self.net.n, topic, sources, blocked,
+                                max_hops, per_peer)
+
     def msg_stats(self) -> list:
         out = np.zeros(4, dtype=np.int64)
         self._check(self.lib.gsim_group_msg_stats(self.g, _ptr(out)))

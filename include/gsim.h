@@ -720,6 +720,52 @@ int gsim_score_report(gsim_handle* h, const struct gsim_score_what_if* what_if,
                       struct gsim_score_cause_row* causes, int64_t cause_cap, int64_t* n_causes,
                       struct gsim_score_topic_row* topics, int64_t topic_cap, int64_t* n_topics);
 
+/* Mesh path report: the mesh of one topic as a graph.  Hop distances from up
+ * to GSIM_PATH_SOURCES sources at once over the routers' mesh links, by a
+ * level-synchronous traversal on the device (one bit per source in a 64-bit
+ * word per peer), with a read-only what-if: the peers of some classes stop
+ * relaying.  The distances are what eager push costs: a router forwards a
+ * message to gs.mesh[topic] (and a publisher outside the topic to
+ * gs.fanout[topic]), gossipsub.go:975-1045, one hop per round.
+ *
+ * Defined on the ABI's edge-order views, with gsim_net_report's convention:
+ * for topic t the mesh digraph has an arc i -> j for edge e of row i with
+ * col[e] = j iff GSIM_F_TFLAGS[t][e] & GSIM_TF_MESH, i announces t (sub bit)
+ * and j announces t; connection state is not consulted.  A source that
+ * announces t starts at hop 0 and expands over its arcs.  A source that does
+ * not (a fanout publisher) expands once, at level 0, over its GSIM_TF_FANOUT
+ * edges into peers that announce t, and is itself neither reached nor a
+ * subscriber.  hops(s, p) is the BFS distance.
+ *   blocked   a bit mask over the peer classes (gsim_set_peer_classes).  A peer
+ *             whose class is in it is reached and counted but never expanded,
+ *             unless it is the source itself (which forwards its own
+ *             publication).  0: the plain distances.
+ *   max_hops  0: until every frontier is empty.  > 0: that many levels; peers
+ *             further away count as unreached and `truncated` is set in the
+ *             rows whose frontier (the unblocked peers at distance max_hops)
+ *             was not empty.
+ * Duplicated sources are allowed; their rows are equal. */
+#define GSIM_PATH_SOURCES 64
+struct gsim_mesh_path_row {                 /* one per source, in the caller's order */
+    uint32_t source, topic;
+    uint32_t reached;                       /* peers announcing topic with a finite distance (the source if it announces) */
+    uint32_t subscribers;                   /* peers announcing topic */
+    uint32_t max_hops;                      /* largest finite distance, exact */
+    uint32_t truncated;                     /* 1: max_hops stopped a non-empty frontier */
+    uint32_t reached_cls[GSIM_NET_CLASSES]; /* reached, by the reached peer's class */
+    uint32_t members_cls[GSIM_NET_CLASSES]; /* subscribers, by class */
+    uint32_t hist[GSIM_REPORT_BINS];        /* hist[d], d < 31: peers at distance d; [31]: >= 31; sum == reached */
+};  /* 184 bytes, reached_cls at offset 24, members_cls at 40, hist at 56 */
+/* 1 <= n_sources <= GSIM_PATH_SOURCES.  GSIM_EINVAL: a source >= N, a topic
+ * outside 0..T-1, a `blocked` bit at or above the class count, a negative
+ * max_hops.  reach_count / hop_sum ([N] each, or NULL): per peer, how many of
+ * the sources reach it and the sum of its finite distances (0 for a peer no
+ * source reaches).  GSIM_ESTATE before gsim_load_graph.  Changes no state;
+ * synchronizes (one counted host read per level). */
+int gsim_mesh_paths(gsim_handle* h, int32_t topic, const uint32_t* sources, int32_t n_sources,
+                    uint32_t blocked, int32_t max_hops, struct gsim_mesh_path_row* rows,
+                    uint32_t* reach_count, uint32_t* hop_sum);
+
 /* ---- trace export (pb/trace.proto, trace.go) ------ */
 /* The events the routers [peer_lo, peer_hi) hand their tracer
  * (pubsubTracer, trace.go:70-530), one record each, in the order of
@@ -1100,6 +1146,18 @@ int gsim_group_score_report(gsim_group* g, const struct gsim_score_what_if* what
                             struct gsim_score_part_row*  parts,  int64_t part_cap,  int64_t* n_parts,
                             struct gsim_score_cause_row* causes, int64_t cause_cap, int64_t* n_causes,
                             struct gsim_score_topic_row* topics, int64_t topic_cap, int64_t* n_topics);
+/* gsim_mesh_paths over a sharded network: sources and the per-peer arrays in
+ * global ids.  Every shard expands the frontier of the peers it owns over its
+ * own rows; the bits that land on its ghosts go to their owners between the
+ * levels (through the host: the ghost ranges are read, the ids translated, the
+ * words ORed in before the owner's fold), every shard counts the new bits of
+ * its owned peers and the rows are summed on the host (max_hops the maximum,
+ * truncated the OR).  Needs every shard in this process (gsim_group_create,
+ * or the host-staged transport in one process); a group whose shards span
+ * processes: GSIM_ESTATE. */
+int gsim_group_mesh_paths(gsim_group* g, int32_t topic, const uint32_t* sources, int32_t n_sources,
+                          uint32_t blocked, int32_t max_hops, struct gsim_mesh_path_row* rows,
+                          uint32_t* reach_count, uint32_t* hop_sum);
 int gsim_group_synchronize(gsim_group* g);
 /* WithPeerScoreInspect over a sharded network (score.go:152-180, 448-500):
  * the whole network's view, filled from the rows this process's shards own
