@@ -1270,6 +1270,7 @@ int gsim_destroy(gsim_handle* h)
     peerreport_release(h);
     scorereport_release(h);
     meshpaths_release(h);
+    relayreport_release(h);
     dfree(h->d_tp);
     dfree(h->d_flags);
     for (auto& ev : h->ev)

@@ -466,6 +466,7 @@ struct NetReport;  // the network report's peer classes and device scratch (netr
 struct PeerReport; // the peer delivery report's device scratch (peerreport.hip)
 struct ScoreReport; // the score report's device scratch and what-if tables (scorereport.hip)
 struct MeshPaths;   // the mesh path report's per-peer words and counters (meshpaths.hip)
+struct RelayReport; // the relay report's device scratch (relayreport.hip)
 using MsgReport = struct ::gsim_msg_report;   // (the call gsim_msg_report hides the struct's name in C++)
 
 // The peer gater's device state as the delivery kernels see it (gater.hip;
@@ -608,6 +609,7 @@ struct gsim_handle {
     gsim::PeerReport* pr = nullptr; // gsim_peer_report scratch (peerreport.hip), allocated at the first call
     gsim::ScoreReport* sr = nullptr; // gsim_score_report scratch (scorereport.hip), allocated at the first call
     gsim::MeshPaths* mp = nullptr;   // gsim_mesh_paths scratch (meshpaths.hip), allocated at the first call; a new graph drops it
+    gsim::RelayReport* rl = nullptr; // gsim_relay_report scratch (relayreport.hip), allocated at the first call
 
     // owned peers / observer rows (all of them unless sharded)
     int64_t olo() const { return sh ? sh->own_lo : 0; }
@@ -780,6 +782,21 @@ int meshpaths_fold(gsim_handle* h, int32_t level, const uint64_t* inc, uint64_t*
 // the rows (source / topic as given) and the per-peer arrays over the local peers ([n] each, or nullptr)
 int meshpaths_finish(gsim_handle* h, const uint32_t* sources, uint64_t truncated, struct gsim_mesh_path_row* rows,
                      uint32_t* reach_count, uint32_t* hop_sum);
+// relayreport.hip: the relay report (gsim_relay_report) in steps, which
+// gsim_group_relay_report (shard.hip) interleaves with the ghosts' exchange
+void relayreport_release(gsim_handle* h);
+int64_t relay_budget(const gsim_handle* h);                            // bytes of per-batch scratch
+// commits the pending claims and selects: *nsel messages, *nc = T * C class rows; synchronizes
+int relay_begin(gsim_handle* h, int64_t round_lo, int64_t round_hi, int64_t* nsel, int64_t* nc);
+// scratch for batches of B slots, zeroed accumulators; rows of the owned local peers [olo, ohi) (empty: none)
+int relay_prepare(gsim_handle* h, int64_t B, int64_t olo, int64_t ohi, bool want_cls, bool want_msgs, bool staged);
+int relay_push(gsim_handle* h, int64_t k0, int32_t nb);                // the batch's cells -> child counts
+int relay_read_counts(gsim_handle* h, int32_t nb, uint32_t* host);     // [nb][n]; synchronizes
+int relay_add_counts(gsim_handle* h, int32_t nb, const uint32_t* inc); // += a host [nb][n]
+int relay_fold(gsim_handle* h, int64_t k0, int32_t nb);                // counts -> rows
+int relay_depth(gsim_handle* h, int64_t k0, int32_t nb);               // the depth passes (single engine)
+int relay_finish(gsim_handle* h, struct gsim_relay_row* peers, uint64_t* cto, struct gsim_relay_class_row* classes,
+                 struct gsim_relay_msg_row* msgs);
 int64_t deliver_last_round_time(gsim_handle* h);   // time of the last round run (INT64_MAX: none yet)
 void trace_release(gsim_handle* h);   // trace.hip
 // round stages (deliver.hip; gsim_round runs them in order, a sharded group

@@ -39,6 +39,7 @@
 #include "gsim.h"
 #include "gsim_internal.h"
 #include "meshpaths_merge.h"
+#include "relayreport_merge.h"
 #include "netreport_merge.h"
 #include "scorereport_merge.h"
 #include "peerreport_merge.h"
@@ -2390,6 +2391,132 @@ int gsim_group_peer_report(gsim_group* g, int64_t round_lo, int64_t round_hi, in
     }
     if (want_cls && merge_peer_reports(pp.data(), got.data(), L, (size_t)nc, classes))
         return g->fail(GSIM_ESTATE, "the shards disagree about a class row's key or messages");
+    return GSIM_OK;
+}
+
+// gsim_relay_report over the group (relayreport.hip's steps), peer rows and
+// class rows: every shard pushes the cells of the peers it owns into its child
+// counts, indexed by local peer id; a parent may be a ghost, so between the
+// push and the fold of a batch the ghosts' counts are read from every shard,
+// translated to their owners' local ids (gid) and added there, and every owner
+// folds the total children of its own peers.  The children by class of a ghost
+// sender reach its owner's row on the host at the end; the class rows are merged
+// on the host (relayreport_merge.cpp).
+int gsim_group_relay_report(gsim_group* g, int64_t round_lo, int64_t round_hi, int64_t peer_lo, int64_t peer_hi,
+                            struct gsim_relay_row* peers, struct gsim_relay_class_row* classes, int64_t class_cap,
+                            int64_t* n_classes, int64_t* n_msgs)
+{
+    if (!g || !n_classes || !n_msgs || class_cap < 0) return GSIM_EINVAL;
+    *n_classes = *n_msgs = 0;
+    if (!g->msgs || g->hs.empty()) return g->fail(GSIM_ESTATE, "gsim_group_msgs_init not called");
+    if ((int)g->hs.size() != g->K)
+        return g->fail(GSIM_ESTATE, "gsim_group_relay_report: the group's shards span processes (the exchange of the "
+                                    "ghosts' child counts needs every shard in this process)");
+    if (peer_lo < 0 || peer_lo > peer_hi || peer_hi > g->N)
+        return g->fail(GSIM_EINVAL, "gsim_group_relay_report: the peer range must satisfy 0 <= peer_lo <= peer_hi <= N");
+    const size_t L = g->hs.size();
+    int64_t nc = 0, cnt = 0, nmax = 1;
+    int rc;
+    for (size_t l = 0; l < L; ++l) {
+        int64_t c1 = 0, n1 = 0;
+        if ((rc = relay_begin(g->hs[l], round_lo, round_hi, &n1, &c1))) {
+            if (l == 0) *n_classes = c1;
+            return g->take(g->hs[l], rc);
+        }
+        if (l == 0) { nc = c1; cnt = n1; *n_classes = nc; *n_msgs = cnt; }
+        else if (c1 != nc || n1 != cnt) return g->fail(GSIM_ESTATE, "the shards disagree about the report's rows or messages");
+        nmax = std::max<int64_t>(nmax, g->hs[l]->n);
+    }
+    const bool want_cls = classes && class_cap > 0, want_peers = peers && peer_hi > peer_lo;
+    if (want_cls && class_cap < nc) return g->fail(GSIM_ERANGE, "gsim_group_relay_report: class row buffer too small");
+    if (!want_cls && !want_peers) return GSIM_OK;
+    std::vector<size_t> local_of((size_t)g->K, 0);                 // shard id -> index in hs
+    for (size_t l = 0; l < L; ++l) local_of[(size_t)g->ids[l]] = l;
+    auto owner_of = [&](int64_t p) {                               // the shard that owns global peer p
+        return (size_t)(std::upper_bound(g->bounds.begin(), g->bounds.end(), p) - g->bounds.begin() - 1);
+    };
+    // one batch size for every shard: 4 + 2 + 4 bytes per (slot, local peer), the staged counts included
+    const int64_t B = std::min<int64_t>(std::max<int64_t>(relay_budget(g->hs[0]) / (10 * nmax), 1), std::max<int64_t>(cnt, 1));
+    std::vector<int64_t> glo(L, 0), ghi(L, 0);                     // the part of the range each shard owns (global ids)
+    for (size_t l = 0; l < L; ++l) {
+        const ShardCtx* sc = g->hs[l]->sh;
+        const size_t k = (size_t)g->ids[l];
+        glo[l] = std::max(peer_lo, g->bounds[k]);
+        ghi[l] = std::max(glo[l], std::min(peer_hi, g->bounds[k + 1]));
+        const bool rows = want_peers && glo[l] < ghi[l];
+        const int64_t llo = rows ? sc->own_lo + (glo[l] - g->bounds[k]) : 0, lhi = rows ? llo + (ghi[l] - glo[l]) : 0;
+        if ((rc = relay_prepare(g->hs[l], B, llo, lhi, want_cls, false, true))) return g->take(g->hs[l], rc);
+    }
+    std::vector<std::vector<uint32_t>> inc(L);
+    std::vector<uint8_t> dirty(L, 0);
+    std::vector<uint32_t> ghost;
+    for (int64_t k0 = 0; k0 < cnt; k0 += B) {
+        const int32_t nb = (int32_t)std::min<int64_t>(B, cnt - k0);
+        for (size_t l = 0; l < L; ++l)
+            if ((rc = relay_push(g->hs[l], k0, nb))) return g->take(g->hs[l], rc);
+        for (size_t l = 0; l < L; ++l) {
+            inc[l].assign((size_t)(nb * g->hs[l]->n), 0u);
+            dirty[l] = 0;
+        }
+        for (size_t l = 0; l < L; ++l) {                           // the ghosts' counts to their owners
+            gsim_handle* h = g->hs[l];
+            const ShardCtx* sc = h->sh;
+            if (sc->own_hi - sc->own_lo == h->n) continue;         // no ghosts
+            ghost.assign((size_t)(nb * h->n), 0u);
+            if ((rc = relay_read_counts(h, nb, ghost.data()))) return g->take(h, rc);
+            for (int64_t x = 0; x < h->n; ++x) {
+                if (x >= sc->own_lo && x < sc->own_hi) continue;
+                const int64_t p = g->gid[l][(size_t)x];
+                const size_t o = owner_of(p), lo = local_of[o];
+                const int64_t y = g->hs[lo]->sh->own_lo + (p - g->bounds[o]), no = g->hs[lo]->n;
+                for (int32_t b = 0; b < nb; ++b) {
+                    const uint32_t w = ghost[(size_t)(b * h->n + x)];
+                    if (!w) continue;
+                    inc[lo][(size_t)(b * no + y)] += w;
+                    dirty[lo] = 1;
+                }
+            }
+        }
+        for (size_t l = 0; l < L; ++l)
+            if (dirty[l] && (rc = relay_add_counts(g->hs[l], nb, inc[l].data()))) return g->take(g->hs[l], rc);
+        for (size_t l = 0; l < L; ++l)
+            if ((rc = relay_fold(g->hs[l], k0, nb))) return g->take(g->hs[l], rc);
+    }
+    const uint8_t* d_cls = nullptr;
+    const int C = netreport_classes(g->hs[0], &d_cls);
+    const bool by_class = want_peers && C > 1;
+    std::vector<std::vector<gsim_relay_class_row>> parts(L);
+    std::vector<const gsim_relay_class_row*> pp;
+    std::vector<int64_t> got(L, cnt);
+    std::vector<std::vector<uint64_t>> cto(L);
+    int bad = GSIM_OK;
+    for (size_t l = 0; l < L; ++l) {
+        gsim_handle* h = g->hs[l];
+        if (want_cls) parts[l].resize((size_t)nc);
+        if (by_class) cto[l].assign((size_t)(h->n * C), 0ull);
+        const bool rows = want_peers && glo[l] < ghi[l];
+        rc = relay_finish(h, rows ? peers + (glo[l] - peer_lo) : nullptr, by_class ? cto[l].data() : nullptr,
+                          want_cls ? parts[l].data() : nullptr, nullptr);
+        if (rc == GSIM_ESTATE && !bad) bad = g->take(h, rc);        // orphans: the rows are written all the same
+        else if (rc && rc != GSIM_ESTATE) return g->take(h, rc);
+        pp.push_back(parts[l].data());
+    }
+    if (by_class)
+        for (size_t l = 0; l < L; ++l) {                           // a ghost sender's children by class, to its owner's row
+            const gsim_handle* h = g->hs[l];
+            const ShardCtx* sc = h->sh;
+            for (int64_t x = 0; x < h->n; ++x) {
+                if (x >= sc->own_lo && x < sc->own_hi) continue;
+                const int64_t p = g->gid[l][(size_t)x];
+                if (p < peer_lo || p >= peer_hi) continue;
+                for (int c = 0; c < C; ++c) peers[p - peer_lo].children_to[c] += cto[l][(size_t)(x * C + c)];
+            }
+        }
+    if (want_cls && merge_relay_reports(pp.data(), got.data(), L, (size_t)nc, classes))
+        return g->fail(GSIM_ESTATE, "the shards disagree about a class row's key or messages");
+    if (bad) return bad;
+    for (size_t l = 0; l < L; ++l)
+        if ((rc = deliver_check_errors(g->hs[l]))) return g->take(g->hs[l], rc);
     return GSIM_OK;
 }
 

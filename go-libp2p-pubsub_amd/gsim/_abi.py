@@ -182,6 +182,44 @@ PEER_CLASS_ROW_DTYPE = [("topic", "<u4"), ("cls", "<u4"), ("peers", "<u4"), ("me
                         ("lat_max", "<u4"), ("_pad", "<u4"), ("first_from", "<u8", (NET_CLASSES,)),
                         ("hist", "<u8", (REPORT_BINS,))]
 
+RELAY_DELAY_BINS = 8
+
+
+class CRelayRow(Structure):
+    """struct gsim_relay_row (64 bytes): one sender of the relay report."""
+    _fields_ = [("held", c_uint32), ("relayed_msgs", c_uint32), ("max_children", c_uint32), ("_pad", c_uint32),
+                ("children", c_uint64), ("own_children", c_uint64), ("children_to", c_uint64 * NET_CLASSES)]
+
+
+class CRelayClassRow(Structure):
+    """struct gsim_relay_class_row (336 bytes): one (topic, sender class) of the relay report."""
+    _fields_ = [("topic", c_uint32), ("cls", c_uint32), ("peers", c_uint32), ("messages", c_uint32),
+                ("held", c_uint64), ("relayed", c_uint64), ("children", c_uint64),
+                ("max_children", c_uint32), ("_pad", c_uint32),
+                ("children_to", c_uint64 * NET_CLASSES), ("fanout", c_uint64 * REPORT_BINS)]
+
+
+class CRelayMsgRow(Structure):
+    """struct gsim_relay_msg_row (216 bytes): one message's delivery tree."""
+    _fields_ = [("id", c_uint64), ("pub_round", c_int64), ("slot", c_uint32), ("topic", c_uint32),
+                ("origin", c_uint32), ("reached", c_uint32), ("relays", c_uint32), ("max_children", c_uint32),
+                ("max_children_peer", c_uint32), ("depth_max", c_uint32), ("orphans", c_uint32),
+                ("verdict", c_uint8), ("vdelay", c_uint8), ("_pad", c_uint8 * 2),
+                ("depth_hist", c_uint32 * REPORT_BINS), ("delay_hist", c_uint32 * RELAY_DELAY_BINS)]
+
+
+# numpy views of struct gsim_relay_row / gsim_relay_class_row / gsim_relay_msg_row
+RELAY_ROW_DTYPE = [("held", "<u4"), ("relayed_msgs", "<u4"), ("max_children", "<u4"), ("_pad", "<u4"),
+                   ("children", "<u8"), ("own_children", "<u8"), ("children_to", "<u8", (NET_CLASSES,))]
+RELAY_CLASS_ROW_DTYPE = [("topic", "<u4"), ("cls", "<u4"), ("peers", "<u4"), ("messages", "<u4"), ("held", "<u8"),
+                         ("relayed", "<u8"), ("children", "<u8"), ("max_children", "<u4"), ("_pad", "<u4"),
+                         ("children_to", "<u8", (NET_CLASSES,)), ("fanout", "<u8", (REPORT_BINS,))]
+RELAY_MSG_ROW_DTYPE = [("id", "<u8"), ("pub_round", "<i8"), ("slot", "<u4"), ("topic", "<u4"), ("origin", "<u4"),
+                       ("reached", "<u4"), ("relays", "<u4"), ("max_children", "<u4"), ("max_children_peer", "<u4"),
+                       ("depth_max", "<u4"), ("orphans", "<u4"), ("verdict", "u1"), ("vdelay", "u1"),
+                       ("_pad", "u1", (2,)), ("depth_hist", "<u4", (REPORT_BINS,)),
+                       ("delay_hist", "<u4", (RELAY_DELAY_BINS,))]
+
 # gsim.h GSIM_PATH_SOURCES: the mesh path report (gsim_mesh_paths)
 PATH_SOURCES = 64
 
@@ -384,6 +422,10 @@ SIGNATURES = [
     ("gsim_peer_report", c_int32, [c_void_p, c_int64, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_int64,
                                    POINTER(c_int64), POINTER(c_int64)]),
     ("gsim_peer_report_launch", c_int32, [c_void_p, c_void_p]),
+    ("gsim_relay_report", c_int32, [c_void_p, c_int64, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_int64,
+                                    POINTER(c_int64), c_void_p, c_int64, POINTER(c_int64)]),
+    ("gsim_relay_report_budget", c_int32, [c_void_p, c_int64]),
+    ("gsim_relay_report_launch", c_int32, [c_void_p, c_void_p]),
     ("gsim_score_report", c_int32, [c_void_p, POINTER(CScoreWhatIf), c_void_p, c_int32, c_void_p, c_int64,
                                     POINTER(c_int64), c_void_p, c_int64, POINTER(c_int64), c_void_p, c_int64,
                                     POINTER(c_int64)]),
@@ -454,6 +496,8 @@ SIGNATURES = [
                                         c_int64, POINTER(c_int64)]),
     ("gsim_group_peer_report", c_int32, [c_void_p, c_int64, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_int64,
                                          POINTER(c_int64), POINTER(c_int64)]),
+    ("gsim_group_relay_report", c_int32, [c_void_p, c_int64, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_int64,
+                                          POINTER(c_int64), POINTER(c_int64)]),
     ("gsim_group_score_report", c_int32, [c_void_p, POINTER(CScoreWhatIf), c_void_p, c_int32, c_void_p, c_int64,
                                           POINTER(c_int64), c_void_p, c_int64, POINTER(c_int64), c_void_p, c_int64,
                                           POINTER(c_int64)]),

@@ -509,6 +509,48 @@ class Engine:
         (gsim_peer_report; helpers: gsim.report)."""
         return _peer_report_call(self, self.lib.gsim_peer_report, self.h, self.net.n, round_lo, round_hi, peers, classes)
 
+    # struct gsim_relay_row / struct gsim_relay_class_row / struct gsim_relay_msg_row
+    RELAY_ROW_DTYPE = np.dtype(_abi.RELAY_ROW_DTYPE)
+    RELAY_CLASS_ROW_DTYPE = np.dtype(_abi.RELAY_CLASS_ROW_DTYPE)
+    RELAY_MSG_ROW_DTYPE = np.dtype(_abi.RELAY_MSG_ROW_DTYPE)
+
+    def relay_report(self, round_lo: int = 0, round_hi: int | None = None, peers=None, classes: bool = True,
+                     messages: bool = True):
+        """(peer_rows, class_rows, msg_rows): the first-delivery forest of the
+        messages msg_report(round_lo, round_hi) selects, from the sender's
+        side.  Per peer of `peers` (None: every peer; (lo, hi): that range) the
+        messages it held and relayed and the first deliveries it gave, by the
+        class of the receiving child (RELAY_ROW_DTYPE); per (topic, class of
+        the sender) the same over every peer with a fan-out histogram
+        (RELAY_CLASS_ROW_DTYPE); per message its relays, widest holder, exact
+        depth, depth histogram and per-hop delay histogram
+        (RELAY_MSG_ROW_DTYPE).  classes=False / messages=False: an empty array
+        in that place.  Reduced on the device from the seen-set cells
+        (gsim_relay_report; helpers: gsim.report)."""
+        hi = (1 << 63) - 1 if round_hi is None else int(round_hi)
+        lo_p, hi_p = (0, int(self.net.n)) if peers is None else (int(peers[0]), int(peers[1]))
+        nc, nm = ctypes.c_int64(0), ctypes.c_int64(0)
+        fn = self.lib.gsim_relay_report
+        self._check(fn(self.h, int(round_lo), hi, lo_p, hi_p, None, None, 0, ctypes.byref(nc), None, 0, ctypes.byref(nm)))
+        rows = np.zeros(max(hi_p - lo_p, 0), dtype=Engine.RELAY_ROW_DTYPE)
+        cls = np.zeros(nc.value if classes else 0, dtype=Engine.RELAY_CLASS_ROW_DTYPE)
+        msg = np.zeros(nm.value if messages else 0, dtype=Engine.RELAY_MSG_ROW_DTYPE)
+        if len(rows) or len(cls) or len(msg):
+            self._check(fn(self.h, int(round_lo), hi, lo_p, hi_p, _ptr(rows) if len(rows) else None,
+                           _ptr(cls) if len(cls) else None, len(cls), ctypes.byref(nc),
+                           _ptr(msg) if len(msg) else None, len(msg), ctypes.byref(nm)))
+        return rows, cls, msg
+
+    def relay_report_budget(self, nbytes: int = 0):
+        """Debug: the byte budget of relay_report's per-batch scratch (0: the default)."""
+        self._check(self.lib.gsim_relay_report_budget(self.h, int(nbytes)))
+
+    def relay_report_launch(self) -> dict:
+        """How the last relay_report ran (gsim_relay_report_launch)."""
+        out = np.zeros(4, dtype=np.int64)
+        self._check(self.lib.gsim_relay_report_launch(self.h, _ptr(out)))
+        return dict(zip(["batch", "batches", "depth_passes", "messages"], (int(x) for x in out)))
+
     # struct gsim_mesh_path_row
     MESH_PATH_ROW_DTYPE = np.dtype(_abi.MESH_PATH_ROW_DTYPE)
 

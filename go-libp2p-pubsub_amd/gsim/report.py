@@ -4,13 +4,13 @@ Engine.MSG_REPORT_DTYPE, struct gsim_msg_report): pure numpy, no device.
 hist[d] counts the peers a message reached d rounds after its publication,
 d < REPORT_BINS - 1; the last bin holds every later one (its exact extent is
 max_latency).  Further down: the network report's, the peer delivery
-report's, the mesh path report's and the score report's rows
-(Engine.net_report, Engine.peer_report, Engine.mesh_paths,
-Engine.score_report)."""
+report's, the relay report's, the mesh path report's and the score report's
+rows (Engine.net_report, Engine.peer_report, Engine.relay_report,
+Engine.mesh_paths, Engine.score_report)."""
 import numpy as np
 
-from ._abi import (NET_CLASSES, NET_DEG_BINS, NET_OUT_BINS, NET_SCORE_BINS, REPORT_BINS, SR_BINS, SR_CAUSES,
-                   SR_PARTS)
+from ._abi import (NET_CLASSES, NET_DEG_BINS, NET_OUT_BINS, NET_SCORE_BINS, RELAY_DELAY_BINS, REPORT_BINS, SR_BINS,
+                   SR_CAUSES, SR_PARTS)
 
 
 def coverage(rep: np.ndarray) -> np.ndarray:
@@ -146,6 +146,87 @@ def class_latency_quantile(class_rows: np.ndarray, q: float):
     <= d, and the overflow flag (True where the quantile falls in the last bin,
     whose latency reads REPORT_BINS - 1, a lower bound)."""
     return latency_quantile(class_rows, q)
+
+
+# ---- relay report (Engine.relay_report: struct gsim_relay_row / _class_row / _msg_row) ----
+
+def _bin_quantile(hist: np.ndarray, q: float):
+    """latency_quantile's rule on an [n, bins] histogram: (bin, overflow)."""
+    if not 0.0 <= q <= 1.0:
+        raise ValueError("q must lie in [0, 1]")
+    hist = hist.astype(np.int64)
+    cum = np.cumsum(hist, axis=1)
+    total = cum[:, -1] if hist.shape[1] else np.zeros(len(hist), dtype=np.int64)
+    need = np.maximum(np.ceil(q * total).astype(np.int64), 1)
+    k = (cum < need[:, None]).sum(axis=1).astype(np.int64)
+    k[total == 0] = 0
+    return k, (k == hist.shape[1] - 1) & (total > 0)
+
+
+def relay_share(class_rows: np.ndarray) -> np.ndarray:
+    """share[t, c]: of the first deliveries of topic t's selected messages, the
+    fraction given by senders of class c ([topics, classes] as the rows name
+    them; a row of nan for a topic without any first delivery)."""
+    T = int(class_rows["topic"].max()) + 1 if len(class_rows) else 0
+    C = int(class_rows["cls"].max()) + 1 if len(class_rows) else 0
+    ch = np.zeros((T, C), dtype=np.float64)
+    np.add.at(ch, (class_rows["topic"].astype(np.int64), class_rows["cls"].astype(np.int64)),
+              class_rows["children"].astype(np.float64))
+    tot = ch.sum(axis=1, keepdims=True)
+    out = np.full((T, C), np.nan)
+    np.divide(ch, tot, out=out, where=tot > 0)
+    return out
+
+
+def leaf_share(class_rows: np.ndarray) -> np.ndarray:
+    """Per class row the share of its holders (q, m) that gave nobody a first
+    delivery, fanout[0] / held; nan where the row holds nothing."""
+    held = class_rows["held"].astype(np.float64)
+    leaves = class_rows["fanout"].astype(np.float64).reshape(len(class_rows), REPORT_BINS)[:, 0]
+    out = np.full(len(class_rows), np.nan)
+    np.divide(leaves, held, out=out, where=held > 0)
+    return out
+
+
+def fanout_quantile(class_rows: np.ndarray, q: float):
+    """Per class row the smallest k with at least q of its holders at a fan-out
+    <= k, read from fanout.  Returns (fanout, overflow): overflow is True where
+    the quantile falls in the last bin (>= REPORT_BINS - 1 children, a lower
+    bound; max_children is exact); a row that holds nothing reads 0."""
+    return _bin_quantile(class_rows["fanout"].reshape(len(class_rows), REPORT_BINS), q)
+
+
+def top_relays(peer_rows: np.ndarray, k: int) -> np.ndarray:
+    """Indices of the k rows with the most children, most first, the lower index
+    first among equals; rows without children are left out."""
+    ch = peer_rows["children"].astype(np.int64)
+    order = np.lexsort((np.arange(len(ch)), -ch))
+    return order[ch[order] > 0][:max(int(k), 0)]
+
+
+def depth_quantile(msg_rows: np.ndarray, q: float):
+    """Per message the smallest depth d with at least q of its placed holders
+    (reached - orphans) at depth <= d, read from depth_hist.  Returns (depth,
+    overflow) as latency_quantile does; depth_max is exact."""
+    return _bin_quantile(msg_rows["depth_hist"].reshape(len(msg_rows), REPORT_BINS), q)
+
+
+def pulled_share(msg_rows: np.ndarray) -> np.ndarray:
+    """Per message the share of its first deliveries whose hop took more than
+    1 + vdelay rounds: those came by IWANT, not by eager push.  nan where a
+    message has no timed delivery.  The last delay bin holds every delay >=
+    RELAY_DELAY_BINS, so a message with 1 + vdelay >= RELAY_DELAY_BINS cannot be
+    answered from the bins: ValueError."""
+    push = 1 + msg_rows["vdelay"].astype(np.int64)
+    if (push >= RELAY_DELAY_BINS).any():
+        raise ValueError("pulled_share: 1 + vdelay reaches the overflow bin (delays >= %d)" % RELAY_DELAY_BINS)
+    hist = msg_rows["delay_hist"].astype(np.float64).reshape(len(msg_rows), RELAY_DELAY_BINS)
+    delay = np.arange(1, RELAY_DELAY_BINS + 1)[None, :]               # bin k holds delay k + 1
+    late = np.where(delay > push[:, None], hist, 0.0).sum(axis=1)
+    tot = hist.sum(axis=1)
+    out = np.full(len(msg_rows), np.nan)
+    np.divide(late, tot, out=out, where=tot > 0)
+    return out
 
 
 # ---- mesh path report (Engine.mesh_paths: struct gsim_mesh_path_row) ----

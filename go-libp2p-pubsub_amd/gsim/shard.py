@@ -471,6 +471,30 @@ class ShardedEngine:
         return _peer_report_call(self, self.lib.gsim_group_peer_report, self.g, self.net.n, round_lo, round_hi, peers,
                                  classes)
 
+    def relay_report(self, round_lo: int = 0, round_hi: int | None = None, peers=None, classes: bool = True):
+        """(peer_rows, class_rows) of Engine.relay_report over the shards of this
+        process: peer ranges and per-peer rows in global ids, class rows merged;
+        a child's parent on another shard counts at its owner
+        (gsim_group_relay_report).  Message rows (depth, delay) are not offered
+        on groups, and every shard must live in this process."""
+        from .engine import Engine
+        hi = (1 << 63) - 1 if round_hi is None else int(round_hi)
+        lo_p, hi_p = (0, int(self.net.n)) if peers is None else (int(peers[0]), int(peers[1]))
+        nc, nm = ctypes.c_int64(0), ctypes.c_int64(0)
+        fn = self.lib.gsim_group_relay_report
+        self._check(fn(self.g, int(round_lo), hi, lo_p, hi_p, None, None, 0, ctypes.byref(nc), ctypes.byref(nm)))
+        rows = np.zeros(max(hi_p - lo_p, 0), dtype=Engine.RELAY_ROW_DTYPE)
+        cls = np.zeros(nc.value if classes else 0, dtype=Engine.RELAY_CLASS_ROW_DTYPE)
+        if len(rows) or len(cls):
+            self._check(fn(self.g, int(round_lo), hi, lo_p, hi_p, _ptr(rows) if len(rows) else None,
+                           _ptr(cls) if len(cls) else None, len(cls), ctypes.byref(nc), ctypes.byref(nm)))
+        return rows, cls
+
+    def relay_report_budget(self, nbytes: int = 0):
+        """Debug: the byte budget of relay_report's per-batch scratch, taken from
+        the first local shard (0: the default)."""
+        self._check(self.lib.gsim_relay_report_budget(self._shard_handle(int(self.local[0])), int(nbytes)))
+
     def mesh_paths(self, topic: int, sources, blocked=(), max_hops: int = 0, per_peer: bool = False):
         """Engine.mesh_paths over the shards of this process: sources and the
         per-peer arrays in global ids, the frontiers exchanged between the

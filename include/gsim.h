@@ -612,6 +612,89 @@ int gsim_peer_report(gsim_handle* h, int64_t round_lo, int64_t round_hi,
  * partial sums meet in atomics on the rows), selected messages}. */
 int gsim_peer_report_launch(gsim_handle* h, int64_t* out3);
 
+/* Relay report: the first-delivery forest read from the sender's side.  Every
+ * committed seen-set cell names the peer whose copy the receiver saw first, so
+ * the tree that actually delivered each message still in the ring is resident
+ * on the device; this call counts who carried it (the quantity P2 rewards,
+ * markFirstMessageDelivery, score.go:919-946, summed at the credited peer), how
+ * wide and how deep the trees are and how many rounds each hop took.  No
+ * [ring][N] view is built.
+ *
+ * Defined on the ABI's views.  Selection and pending claims as
+ * gsim_peer_report's.  For a selected message m with origin o and a peer p
+ * holding a committed cell:
+ *   parent(p)      the cell's first sender; the origin's cell has none.
+ *   children(q, m) the peers whose parent in m is q.
+ *   depth(p)       depth(o) = 0, depth(p) = depth(parent(p)) + 1.  A parent's
+ *                  first-seen round is strictly smaller than its child's (also
+ *                  with vdelay: the cell stores the completion round, forwarding
+ *                  happens a round later), so the structure is a tree.
+ *   orphan         p's parent holds no committed cell in the slot, or one with a
+ *                  round >= p's (or p's cell is older than the publication): p
+ *                  counts in `orphans`, has no depth and no delay, and the call
+ *                  returns GSIM_ESTATE after writing the rows.  Its descendants
+ *                  take their depth from it as a root of depth 0.
+ *   delay(p)       seen[p] - seen[parent(p)] >= 1; a hop of more than 1 + vdelay
+ *                  rounds was pulled (IWANT) rather than pushed.
+ * children counts reach ring * (a sender's degree), past 32 bits at the ABI's
+ * limits (ring 8192, E < 2^30), so every sum of children is a u64; a single
+ * message's children(q, m) is at most q's degree and stays a u32. */
+struct gsim_relay_row {          /* one per peer q of [peer_lo, peer_hi): the sender's side */
+    uint32_t held;               /* selected messages with a committed cell of q                 */
+    uint32_t relayed_msgs;       /* of those, messages with children(q, m) > 0                   */
+    uint32_t max_children;       /* largest children(q, m) of one message                        */
+    uint32_t _pad;
+    uint64_t children;           /* sum over m of children(q, m)                                 */
+    uint64_t own_children;       /* of those, in messages q originated                           */
+    uint64_t children_to[GSIM_NET_CLASSES]; /* children by the class of the receiving child; sum == children */
+};  /* 64 bytes, children at offset 16, children_to at 32 */
+struct gsim_relay_class_row {    /* one per (topic, class of the SENDER), ordered (topic, cls), over every peer */
+    uint32_t topic, cls;
+    uint32_t peers;              /* peers of cls announcing topic now                            */
+    uint32_t messages;           /* selected messages of topic                                   */
+    uint64_t held;               /* (q, m): q of cls holds a committed cell of m                 */
+    uint64_t relayed;            /* of those, children(q, m) > 0                                 */
+    uint64_t children;           /* first deliveries given by senders of cls                     */
+    uint32_t max_children, _pad; /* largest children(q, m), exact                                */
+    uint64_t children_to[GSIM_NET_CLASSES]; /* children by the child's class; sum == children     */
+    uint64_t fanout[GSIM_REPORT_BINS]; /* holders by children(q, m) = k < 31; [31]: >= 31; leaves in [0]; sum == held */
+};  /* 336 bytes, children_to at offset 48, fanout at 80 */
+struct gsim_relay_msg_row {      /* one per selected message, ordered (pub_round, slot) */
+    uint64_t id;
+    int64_t  pub_round;
+    uint32_t slot, topic;
+    uint32_t origin;
+    uint32_t reached;            /* peers with a committed cell, the origin included             */
+    uint32_t relays;             /* holders with at least one child                              */
+    uint32_t max_children;       /* the widest holder's children ...                             */
+    uint32_t max_children_peer;  /* ... and its id, the lowest on a tie (0 when nobody relayed)  */
+    uint32_t depth_max;          /* exact                                                        */
+    uint32_t orphans;
+    uint8_t  verdict, vdelay, _pad[2];
+    uint32_t depth_hist[GSIM_REPORT_BINS]; /* depth d < 31 in [d], >= 31 in [31]; sum == reached - orphans */
+    uint32_t delay_hist[8];      /* delays 1..7 in [0..6], >= 8 in [7]; sum == reached - 1 - orphans */
+};  /* 216 bytes, depth_hist at offset 56, delay_hist at 184 */
+/* Any of the three outputs may be NULL (or its cap 0) to skip that part; all
+ * three skipped: the call only counts.  *n_classes = T * C and *n_msgs, the
+ * selected messages, are always set; a cap that is too small: GSIM_ERANGE,
+ * nothing written.  peers: peer_hi - peer_lo rows; a range outside 0 <= peer_lo
+ * <= peer_hi <= N: GSIM_EINVAL.  GSIM_ESTATE before gsim_msgs_init.  The class
+ * and message rows cover every peer whatever the peer range.  Message rows need
+ * every latency below 16383 rounds (else GSIM_ERANGE, rows written).  A first
+ * sender that is no local peer: GSIM_ESTATE.  Changes no state; synchronizes;
+ * returns gsim_msg_stats's GSIM_ERANGE / GSIM_ESTATE (rows written) when the
+ * delivery error flags are set. */
+int gsim_relay_report(gsim_handle* h, int64_t round_lo, int64_t round_hi,
+                      int64_t peer_lo, int64_t peer_hi, struct gsim_relay_row* peers,
+                      struct gsim_relay_class_row* classes, int64_t class_cap, int64_t* n_classes,
+                      struct gsim_relay_msg_row* msgs, int64_t msg_cap, int64_t* n_msgs);
+/* Debug: the byte budget of the per-batch scratch (6 bytes per (slot of the
+ * batch, peer); 0: the default, 256 MiB).  The results do not depend on it. */
+int gsim_relay_report_budget(gsim_handle* h, int64_t bytes);
+/* Debug accessor of the last gsim_relay_report that ran: out4 = {slots per
+ * batch, batches, depth passes in all, selected messages}. */
+int gsim_relay_report_launch(gsim_handle* h, int64_t* out4);
+
 /* Score report: why a score is what it is.  The live score of every record
  * decomposed into the reference's P1..P7 (score.go:265-342) as distributions
  * per (observer class, subject class), reduced on the device in one read-only
@@ -1135,6 +1218,19 @@ int gsim_group_peer_report(gsim_group* g, int64_t round_lo, int64_t round_hi,
                            int64_t peer_lo, int64_t peer_hi, struct gsim_peer_row* peers,
                            struct gsim_peer_class_row* classes, int64_t class_cap,
                            int64_t* n_classes, int64_t* n_msgs);
+/* gsim_relay_report over a sharded network: peer rows (global ids) and class
+ * rows only.  Every shard walks the cells of the peers it owns; a parent may be
+ * a ghost, so between the push and the fold of a batch the ghosts' child counts
+ * are read and added into their owners' scratch through the host, and every
+ * owner folds the total children(q, m) of its own peers.  A ghost parent's cell
+ * is not checked for orphans.  Class rows are merged on the host (sums,
+ * max_children the maximum; disagreeing keys, messages or selected counts:
+ * GSIM_ESTATE).  Needs every shard in this process; a group whose shards span
+ * processes: GSIM_ESTATE. */
+int gsim_group_relay_report(gsim_group* g, int64_t round_lo, int64_t round_hi,
+                            int64_t peer_lo, int64_t peer_hi, struct gsim_relay_row* peers,
+                            struct gsim_relay_class_row* classes, int64_t class_cap,
+                            int64_t* n_classes, int64_t* n_msgs);
 /* gsim_score_report over a sharded network: every local shard reports the
  * records of the observers it owns (a ghost subject carries its class and its
  * app-specific score), with the same what-if parameters; the rows are merged
