@@ -1890,6 +1890,7 @@ struct IhArgs {
     int32_t T, ring, R;
     int64_t g, tick;
     int32_t lo_round;              // first round of the gossip window
+    int32_t serve_lo;              // first round of the history window after this heartbeat's Shift
     const uint32_t *row_ptr, *col, *rev;
     const uint64_t* sub;
     const uint64_t* smask;         // topic slots (gsel planes: the advertiser's row)
@@ -1972,18 +1973,6 @@ __device__ __forceinline__ uint32_t member_peer(const IhArgs& a, int32_t t, int6
     return off < 0 ? (uint32_t)j : a.mlist[off + j];
 }
 
-// handleIWant's GetForPeer count (mcache.go:73-86) for a response to
-// (slot m, the advertiser's edge re): only a bad-signature message can be
-// asked for twice (its receivers never see it), and only its origin serves it.
-__device__ __forceinline__ bool peertx_allows(const IhArgs& a, uint32_t m, uint32_t re, uint32_t advertiser)
-{
-    if (a.minv[m] != GSIM_VERDICT_SIGNATURE || !a.peertx) return true;
-    uint8_t* c = a.peertx + (int64_t)m * a.ptx_w + (re - a.row_ptr[advertiser]);
-    const uint32_t n = (uint32_t)*c + 1u;
-    *c = (uint8_t)(n > 255u ? 255u : n);
-    return (int32_t)n <= a.retrans;
-}
-
 // round a cell's message was (or will be) validated and put in the mcache,
 // at control time of round g (any claim still pending is from round g-1 or
 // g and completes L rounds later), or -1
@@ -1993,6 +1982,26 @@ __device__ __forceinline__ int64_t cell_round(uint64_t c, int64_t g, uint32_t L 
     const uint32_t hi = (uint32_t)(c >> 32);
     if (!(hi & kClaim)) return hi;
     return ((((hi >> 30) & 1u) == (uint32_t)(g & 1)) ? g : g - 1) + L;
+}
+
+// handleIWant's GetForPeer count (mcache.go:73-86) for a response to
+// (slot m, the advertiser's edge re): only a bad-signature message can be
+// asked for twice (its receivers never see it), and only its origin serves it.
+__device__ __forceinline__ bool peertx_allows(const IhArgs& a, uint32_t m, uint32_t re, uint32_t advertiser)
+{
+    // mcache.Shift (mcache.go:94-104) runs between the IHAVE and the IWANT: with HistoryGossip ==
+    // HistoryLength the oldest advertised window has left the cache (GetForPeer finds nothing, no count)
+    // (cell_round without the message's validation latency, which holds_in_window passes: a cell
+    // still pending is a claim of round g - 1 or g, far above serve_lo with or without it, and
+    // the advertiser passed fr < tick_round to advertise at all)
+    if (a.serve_lo > a.lo_round &&
+        cell_round(a.cs.get(m, (int32_t)a.mtopic[m], advertiser), a.g) < (int64_t)a.serve_lo)
+        return false;
+    if (a.minv[m] != GSIM_VERDICT_SIGNATURE || !a.peertx) return true;
+    uint8_t* c = a.peertx + (int64_t)m * a.ptx_w + (re - a.row_ptr[advertiser]);
+    const uint32_t n = (uint32_t)*c + 1u;
+    *c = (uint8_t)(n > 255u ? 255u : n);
+    return (int32_t)n <= a.retrans;
 }
 
 constexpr int kRespStage = 256;    // per-wave LDS staging of queued responses
@@ -3758,6 +3767,7 @@ static bool ihave_prepare(gsim_handle* h, int64_t g, IhaveStage* st, int* rc)
     a.N = h->n; a.E = h->e; a.T = h->t; a.ring = d->cfg.ring; a.R = d->cfg.rounds;
     a.g = g; a.tick = tick;
     a.lo_round = (int32_t)std::max<int64_t>((tick - h->gp.history_gossip) * d->cfg.rounds, 0);
+    a.serve_lo = (int32_t)std::max<int64_t>((tick - h->gp.history_length + 1) * d->cfg.rounds, 0);
     a.row_ptr = h->d_row_ptr; a.col = h->d_col; a.rev = h->d_rev; a.sub = h->d_sub; a.smask = h->d_smask;
     a.mtopic = d->d_mtopic; a.morigin = d->d_morigin; a.minv = d->d_minv;
     a.mlat = d->lat_on ? d->d_mlat : nullptr;

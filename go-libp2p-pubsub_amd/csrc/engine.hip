@@ -1208,6 +1208,33 @@ static int create_impl(const gsim_peer_score_params* params, const gsim_topic_sc
                       gossip->history_gossip, gossip->history_length);
         return fail(GSIM_EINVAL, buf);
     }
+    // The heartbeat's closed forms restate the reference's loops for the degree
+    // parameters it documents (0 <= Dlo <= D <= Dhi, Dout <= D: beyond D the
+    // keep-set of the Dhi prune stops matching the rotation of
+    // gossipsub.go:1452-1483); settings at which the reference indexes a slice
+    // out of range (a negative D, Dscore or Dlazy) have no result to restate.
+    {
+        const char* bad = nullptr;
+        if (gossip->d < 0) bad = "D must not be negative";
+        else if (gossip->dlo > gossip->d) bad = "Dlo must not exceed D";
+        else if (gossip->d > gossip->dhi) bad = "D must not exceed Dhi";
+        else if (gossip->dout > gossip->d) bad = "Dout must not exceed D (gossipsub.go:90: Dout must be set below Dlo, and must not exceed D / 2)";
+        else if (gossip->dscore < 0) bad = "Dscore must not be negative";
+        else if (gossip->dlazy < 0) bad = "Dlazy must not be negative";
+        if (bad) {
+            std::snprintf(buf, sizeof buf, "invalid mesh degree parameters; %s (D %d, Dlo %d, Dhi %d, Dscore %d, Dout %d, Dlazy %d)",
+                          bad, gossip->d, gossip->dlo, gossip->dhi, gossip->dscore, gossip->dout, gossip->dlazy);
+            return fail(GSIM_EINVAL, buf);
+        }
+    }
+    if (gossip->do_px && gossip->prune_peers < 1) {
+        // getPeers(topic, PrunePeers, ...) lists every topic peer when the count is <= 0
+        // (gossipsub.go:1923); the engine's PX lists are bounded by PrunePeers
+        std::snprintf(buf, sizeof buf,
+                      "invalid parameters for peer exchange; PrunePeers (%d) must be at least 1 with PeerExchange on "
+                      "(the reference lists every topic peer then, gossipsub.go:1923)", gossip->prune_peers);
+        return fail(GSIM_EINVAL, buf);
+    }
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
         return fail(GSIM_EDEVICE, "no HIP device available (the engine has no CPU fallback)");

@@ -543,6 +543,7 @@ __device__ __forceinline__ bool gossip_targets(const HbArgs& a, bool cand, bool 
     int target = a.dlazy;
     const int factor = (int)(a.gossip_factor * (double)n);
     if (factor > target) target = factor;
+    if (target <= 0) return false;   // peers[:0]: nobody (select's count <= 0 means all, getPeers' convention)
     if (target >= n) return cand || dup;
     // each lane holds up to two instances (candidate, fill duplicate)
     // no fill duplicates (the usual case): one instance per lane
@@ -795,6 +796,7 @@ struct BlockGroup {
         int target = a.dlazy;
         const int factor = (int)(a.gossip_factor * (double)n);
         if (factor > target) target = factor;
+        if (target <= 0) return;            // peers[:0]: nobody (select's count <= 0 means all)
         if (target >= n) {
 #pragma unroll
             for (int v = 0; v < V; ++v) sel[v] = cand[v] || dup[v];
@@ -3481,6 +3483,7 @@ struct WideRow {
         int target = a.dlazy;
         const int factor = (int)(a.gossip_factor * (double)n);
         if (factor > target) target = factor;
+        if (target <= 0) return;            // peers[:0]: nobody (WC_GS is clear; select's count <= 0 means all)
         if (target >= n) {
             for (int q = tid; q < deg; q += kWideB) set(bits2, q, WC_GS, (bits[q] & WB_CAND) || (bits2[q] & WC_DUP));
             return;

@@ -154,6 +154,11 @@ typedef struct gsim_handle gsim_handle;
  * WithGossipSubParams (gossipsub.go:398-411) + newPeerScore (score.go:183-195).
  * Validates like the reference (GSIM_EINVAL + message; the message is also
  * written to err when err != NULL since no handle exists on failure).
+ * Also GSIM_EINVAL, before a device is asked for: HistoryGossip >
+ * HistoryLength; D < 0, Dlo > D, D > Dhi, Dout > D (gossipsub.go:90), Dscore < 0
+ * or Dlazy < 0 (the heartbeat restates the reference's loops for the
+ * documented order of the degree parameters); PrunePeers < 1 with do_px (the
+ * reference then lists every topic peer, gossipsub.go:1923).
  * device: HIP device ordinal. */
 int gsim_create(const gsim_peer_score_params* params,
                 const gsim_topic_score_params* topics, int32_t n_topics,

@@ -236,6 +236,48 @@ void    orc_msgs_log(orc_msgs* m, int32_t on);
 int64_t orc_msgs_events(orc_msgs* m, orc_event* out, int64_t cap);   /* copies and clears; returns the count */
 int64_t orc_msgs_ihave_marks(orc_msgs* m, uint8_t* out, int64_t n);   /* last heartbeat's [T][E] IHAVE marks */
 
+/* ---- branch census ------------------------------------------------------ */
+/* A parity test proves nothing about a branch it never reached.  With the
+ * census on, the heartbeat counts the (observer, topic) events that took each
+ * branch below, per row class of the observer (its number of connections: up
+ * to 8, 9-16, 17-32, ..., 4097-8192, over 8192).  One global table, off by
+ * default; updates are atomic (the heartbeat is an OpenMP loop). */
+enum {
+    ORC_CB_NEG_PRUNE = 0,    /* a mesh peer with a negative score pruned (1403-1410) */
+    ORC_CB_DLO_ALL,          /* Dlo graft took every candidate (at least one) (1412-1427) */
+    ORC_CB_DLO_TRUNC,        /* ... took D - l of more candidates */
+    ORC_CB_DHI_PRUNE,        /* mesh over Dhi pruned to D (1429-1490) */
+    ORC_CB_ROT_PASS1,        /* the Dout rotation's first loop moved a peer (1463-1472) */
+    ORC_CB_ROT_PASS2,        /* ... its second loop moved a peer (1475-1482) */
+    ORC_CB_DOUT_GRAFT,       /* outbound quota graft of at least one peer (1492-1518) */
+    ORC_CB_OPP_ALL,          /* opportunistic graft took every candidate (at least one) (1520-1552) */
+    ORC_CB_OPP_TRUNC,        /* ... took OpportunisticGraftPeers of more candidates */
+    ORC_CB_GOSSIP_ALL,       /* emitGossip: target >= len(peers) > 0: all of the list (1755-1756) */
+    ORC_CB_GOSSIP_SELECT,    /* ... 0 < target < len(peers), no fill */
+    ORC_CB_GOSSIP_FILL,      /* ... the Dlo fill appended at least one peer (1739-1748) */
+    ORC_CB_GOSSIP_TWO,       /* ... fill and 0 < target < len(peers): selection over two instances */
+    ORC_CB_GOSSIP_BOTH,      /* ... which took one peer through both its instances */
+    ORC_CB_GOSSIP_ZERO,      /* ... target == 0 with a list: nobody */
+    ORC_CB_FANOUT_TOPUP,     /* fanout maintenance added at least one peer (1578-1591) */
+    ORC_CB_PX_FULL,          /* makePrune's list held every candidate (at least one) */
+    ORC_CB_PX_TRUNC_SMALL,   /* ... PrunePeers of at most 64 candidates */
+    ORC_CB_PX_TRUNC_BIG,     /* ... PrunePeers of more than 64 candidates */
+    ORC_CB_COUNT
+};
+#define ORC_CENSUS_CLASSES 12
+void orc_census_enable(int on);
+void orc_census_reset(void);
+void orc_census_read(uint64_t* out);     /* [ORC_CB_COUNT][ORC_CENSUS_CLASSES] */
+
+/* The selection keys, for tests that restate a selection as "sort by key":
+ * the key of item `col` at row position `pos` in the shuffle `purpose` of
+ * (tick, observer, topic), and makePrune's key of a PX candidate (the purpose
+ * is 14 for the heartbeat's PRUNEs; pruned_pos: the pruned peer's row position). */
+uint64_t orc_select_key(uint64_t seed, uint64_t tick, uint32_t obs, int32_t topic, uint32_t purpose, uint32_t col,
+                        uint32_t pos);
+uint64_t orc_px_key(uint64_t seed, uint64_t tick, uint32_t obs, int32_t topic, uint32_t purpose, uint32_t col,
+                    uint32_t pruned_pos, uint32_t pos);
+
 /* ---- mcache.go (one router's MessageCache) ------------------------------ */
 typedef struct orc_mcache orc_mcache;
 orc_mcache* orc_mcache_new(int32_t gossip, int32_t history);            /* mcache.go:21-36 */

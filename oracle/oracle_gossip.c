@@ -135,6 +135,7 @@ void orc_gossip_emit(orc_net* s, orc_msgs* m, uint32_t i, int32_t t, uint64_t ti
         L[n].v = e;
         ++n;
     }
+    const int nc = n;                    /* the candidates; the rest of L are fill instances */
     if (n < gp->dlo) {
         /* fill from the topic peers in map order until Dlo (gossipsub.go:1739-1748);
          * peers already selected can be appended again */
@@ -159,8 +160,21 @@ void orc_gossip_emit(orc_net* s, orc_msgs* m, uint32_t i, int32_t t, uint64_t ti
     int target = gp->dlazy;
     const int factor = (int)(gp->gossip_factor * (double)n);
     if (factor > target) target = factor;
+    if (orc_census_on && n > 0) {
+        const int filled = n > nc;
+        if (filled) orc_census(ORC_CB_GOSSIP_FILL, deg);
+        if (target <= 0) orc_census(ORC_CB_GOSSIP_ZERO, deg);
+        else if (target >= n) orc_census(ORC_CB_GOSSIP_ALL, deg);
+        else orc_census(filled ? ORC_CB_GOSSIP_TWO : ORC_CB_GOSSIP_SELECT, deg);
+    }
     if (target > n) target = n;
     else qsort(L, (size_t)n, sizeof(kv), cmp_kv);                           /* shufflePeers */
+    if (orc_census_on && n > nc && target > 0 && target < n) {
+        int both = 0;                    /* (a filled list is shorter than Dlo) */
+        for (int q = 1; q < target && !both; ++q)
+            for (int r = 0; r < q; ++r) both |= L[r].v == L[q].v;
+        if (both) orc_census(ORC_CB_GOSSIP_BOTH, deg);
+    }
     for (int q = 0; q < target; ++q) p->ihave[te(s, t, s->rev[L[q].v])] = 1;  /* enqueueGossip */
     free(L);
 }

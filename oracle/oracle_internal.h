@@ -106,6 +106,27 @@ void orc_log(orc_msgs* m, int32_t kind, uint32_t a, uint32_t b, uint32_t slot, i
 void orc_log_net(int32_t kind, uint32_t a, uint32_t b, int32_t topic, int64_t now);
 void orc_log_net_x(int32_t kind, uint32_t a, uint32_t b, int32_t topic, uint64_t mid, int64_t g, int64_t x);
 
+/* ---- branch census (oracle.h: orc_census_*) ----------------------------- */
+/* The row classes restate the engine's heartbeat dispatch by row length:
+ * up to 8, 9-16, 17-32, ..., 4097-8192, over 8192 (twelve classes). */
+extern int32_t orc_census_on;
+extern uint64_t orc_census_tab[ORC_CB_COUNT][ORC_CENSUS_CLASSES];
+
+static inline int orc_row_class(uint32_t deg)
+{
+    int c = 0;
+    for (uint32_t hi = 8; c < ORC_CENSUS_CLASSES - 1 && deg > hi; hi *= 2) ++c;
+    return c;
+}
+
+/* one (observer, topic) event: one test of the flag when the census is off */
+static inline void orc_census(int branch, uint32_t deg)
+{
+    if (!orc_census_on) return;
+#pragma omp atomic
+    orc_census_tab[branch][orc_row_class(deg)] += 1;
+}
+
 priv* orc_msgs_priv(orc_msgs* m);
 int64_t orc_round_time(const orc_msgs* m, int64_t g);
 

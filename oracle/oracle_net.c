@@ -126,6 +126,9 @@ static int px_list(hb* h, uint32_t ep, int live, uint32_t purpose, uint64_t key_
         ++n;
     }
     qsort(c, (size_t)n, sizeof(cand), cmp_key);
+    if (n > 0)
+        orc_census(n <= s->gp->prune_peers ? ORC_CB_PX_FULL : n <= 64 ? ORC_CB_PX_TRUNC_SMALL : ORC_CB_PX_TRUNC_BIG,
+                   h->en - h->b);
     if (n > s->gp->prune_peers) n = s->gp->prune_peers;
     for (int q = 0; q < n; ++q)
         orc_log_net_x(ORC_EV_PX_PEER, h->i, s->col[c[q].e], h->t, s->col[ep], q, h->now);
@@ -167,29 +170,32 @@ static void px_emit(hb* h, uint32_t ep, int live, uint32_t purpose, uint64_t key
     cand buf[1024];
     cand* c = deg <= 1024 ? buf : (cand*)malloc(sizeof(cand) * deg);
     const int n = px_list(h, ep, live, purpose, key_tick, c);
-    uint32_t listed[256];
-    for (int q = 0; q < n && q < 256; ++q) listed[q] = s->col[c[q].e];
+    /* the list is as long as PrunePeers asks: no cap of its own */
+    uint32_t* listed = (uint32_t*)malloc(sizeof(uint32_t) * (size_t)(n > 0 ? n : 1));
+    for (int q = 0; q < n; ++q) listed[q] = s->col[c[q].e];
     if (c != buf) free(c);
-    if (!pend) {
-        px_accept(s, ep, listed, n < 256 ? n : 256);
+    px_pend* pp = s->px_pend;
+    if (!pend || !pp) {
+        if (!pend) px_accept(s, ep, listed, n);
+        free(listed);
         return;
     }
-    px_pend* pp = s->px_pend;
-    if (!pp) return;
-    for (int q = 0; q < n && q < 256; ++q) {
+    for (int q = 0; q < n; ++q) {
         if (pp->n == pp->cap) {
             pp->cap = pp->cap ? 2 * pp->cap : 256;
             pp->ent = (uint64_t*)realloc(pp->ent, sizeof(uint64_t) * (size_t)pp->cap);
         }
         pp->ent[pp->n++] = (uint64_t)ep | ((uint64_t)listed[q] << 32);
     }
+    free(listed);
 }
 
 typedef int (*filter_fn)(const hb* h, uint32_t e, double arg);
 
 /* getPeers, gossipsub.go:1908-1928: filter the topic peers, shuffle (= order
- * by Philox key), truncate to count when count > 0. */
-static int get_peers(const hb* h, int count, filter_fn f, double arg, uint32_t purpose, cand* out)
+ * by Philox key), truncate to count when count > 0.  total (may be NULL): the
+ * number of peers that passed the filter (for the census). */
+static int get_peers(const hb* h, int count, filter_fn f, double arg, uint32_t purpose, cand* out, int* total)
 {
     int n = 0;
     for (uint32_t e = h->b; e < h->en; ++e) {
@@ -200,8 +206,15 @@ static int get_peers(const hb* h, int count, filter_fn f, double arg, uint32_t p
         ++n;
     }
     qsort(out, (size_t)n, sizeof(cand), cmp_key);
+    if (total) *total = n;
     if (count > 0 && n > count) n = count;
     return n;
+}
+
+/* census of a getPeers-then-graft branch: every candidate taken, or count of more */
+static void census_taken(const hb* h, int n, int total, int all, int trunc)
+{
+    if (n > 0) orc_census(n == total ? all : trunc, h->en - h->b);
 }
 
 static int f_graft(const hb* h, uint32_t e, double arg)      /* gossipsub.go:1416-1422 */
@@ -249,19 +262,24 @@ static void maintain(hb* h)
     cand* c = deg <= 4096 ? buf : (cand*)malloc(sizeof(cand) * deg);
 
     /* drop all peers with negative score, without PX (1403-1410) */
+    int negs = 0;
     for (uint32_t e = h->b; e < h->en; ++e)
-        if (in_mesh(h, e) && s->score[e] < 0) prune_peer(h, e);
+        if (in_mesh(h, e) && s->score[e] < 0) { prune_peer(h, e); ++negs; }
+    if (negs) orc_census(ORC_CB_NEG_PRUNE, deg);
 
     /* do we have enough peers? (1412-1427) */
     int l = mesh_count(h);
     if (l < gp->dlo) {
-        int n = get_peers(h, gp->d - l, f_graft, 0, P_GRAFT_DLO, c);
+        int total;
+        int n = get_peers(h, gp->d - l, f_graft, 0, P_GRAFT_DLO, c, &total);
+        census_taken(h, n, total, ORC_CB_DLO_ALL, ORC_CB_DLO_TRUNC);
         for (int q = 0; q < n; ++q) graft_peer(h, c[q].e);
     }
 
     /* do we have too many peers? (1429-1490) */
     l = mesh_count(h);
     if (l > gp->dhi) {
+        orc_census(ORC_CB_DHI_PRUNE, deg);
         int n = 0;
         for (uint32_t e = h->b; e < h->en; ++e) {
             if (!in_mesh(h, e)) continue;
@@ -279,15 +297,18 @@ static void maintain(hb* h)
         int outbound = 0;
         for (int q = 0; q < gp->d && q < n; ++q) outbound += s->outbound[c[q].e] != 0;
         if (outbound < gp->dout) {
+            int moved1 = 0, moved2 = 0;
             #define ROTATE(idx) do { cand p_ = c[idx]; for (int j_ = (idx); j_ > 0; --j_) c[j_] = c[j_ - 1]; c[0] = p_; } while (0)
             if (outbound > 0) {
                 int ihave = outbound;
                 for (int q = 1; q < gp->d && ihave > 0; ++q)
-                    if (s->outbound[c[q].e]) { ROTATE(q); --ihave; }
+                    if (s->outbound[c[q].e]) { ROTATE(q); --ihave; moved1 = 1; }
             }
             int ineed = gp->dout - outbound;
             for (int q = gp->d; q < n && ineed > 0; ++q)
-                if (s->outbound[c[q].e]) { ROTATE(q); --ineed; }
+                if (s->outbound[c[q].e]) { ROTATE(q); --ineed; moved2 = 1; }
+            if (moved1) orc_census(ORC_CB_ROT_PASS1, deg);
+            if (moved2) orc_census(ORC_CB_ROT_PASS2, deg);
             #undef ROTATE
         }
         for (int q = gp->d; q < n; ++q) {
@@ -304,7 +325,8 @@ static void maintain(hb* h)
         int outbound = 0;
         for (uint32_t e = h->b; e < h->en; ++e) outbound += in_mesh(h, e) && s->outbound[e];
         if (outbound < gp->dout) {
-            int n = get_peers(h, gp->dout - outbound, f_dout, 0, P_GRAFT_DOUT, c);
+            int n = get_peers(h, gp->dout - outbound, f_dout, 0, P_GRAFT_DOUT, c, NULL);
+            if (n > 0) orc_census(ORC_CB_DOUT_GRAFT, deg);
             for (int q = 0; q < n; ++q) graft_peer(h, c[q].e);
         }
     }
@@ -319,7 +341,9 @@ static void maintain(hb* h)
         double median = sc[n / 2];
         free(sc);
         if (median < s->th->opportunistic_graft_threshold) {
-            int m = get_peers(h, gp->opportunistic_graft_peers, f_opp, median, P_GRAFT_OPP, c);
+            int total;
+            int m = get_peers(h, gp->opportunistic_graft_peers, f_opp, median, P_GRAFT_OPP, c, &total);
+            census_taken(h, m, total, ORC_CB_OPP_ALL, ORC_CB_OPP_TRUNC);
             for (int q = 0; q < m; ++q) graft_peer(h, c[q].e);
         }
     }
@@ -366,7 +390,8 @@ static void fanout(hb* h, orc_msgs* m)
             else ++have;
         }
         if (have < gp->d) {
-            const int n = get_peers(h, gp->d - have, f_fanout, thr, P_FANOUT, c);
+            const int n = get_peers(h, gp->d - have, f_fanout, thr, P_FANOUT, c, NULL);
+            if (n > 0) orc_census(ORC_CB_FANOUT_TOPUP, deg);
             for (int q = 0; q < n; ++q) s->tflags[ti(h, c[q].e)] |= GSIM_TF_FANOUT;
         }
         if (m) orc_gossip_emit(s, m, h->i, t, h->tick, h->seed, GSIM_TF_FANOUT);
@@ -388,7 +413,7 @@ void orc_fanout_publish(orc_net* s, uint32_t origin, int32_t topic, int64_t g, i
         cand buf[4096];
         const uint32_t deg = h.en - h.b;
         cand* c = deg <= 4096 ? buf : (cand*)malloc(sizeof(cand) * deg);
-        const int n = get_peers(&h, s->gp->d, f_fanout, s->th->publish_threshold, P_FANOUT_NEW, c);
+        const int n = get_peers(&h, s->gp->d, f_fanout, s->th->publish_threshold, P_FANOUT_NEW, c, NULL);
         for (int q = 0; q < n; ++q) s->tflags[ti(&h, c[q].e)] |= GSIM_TF_FANOUT;
         if (n > 0) s->fan_topics[origin] |= 1ull << topic;
         if (c != buf) free(c);
@@ -699,7 +724,7 @@ void orc_set_subscriptions(orc_net* s, const uint32_t* pairs, int32_t count, int
                     else ++have;
                 }
                 if (have < gp->d) {
-                    const int n = get_peers(&h, gp->d - have, f_join_more, 0, P_JOIN, c);
+                    const int n = get_peers(&h, gp->d - have, f_join_more, 0, P_JOIN, c, NULL);
                     for (int k = 0; k < n; ++k) s->tflags[ti(&h, c[k].e)] |= GSIM_TF_FANOUT;
                 }
                 for (uint32_t e = h.b; e < h.en; ++e)
@@ -708,7 +733,7 @@ void orc_set_subscriptions(orc_net* s, const uint32_t* pairs, int32_t count, int
                 s->fan_topics[p] &= ~bit;                        /* delete(gs.fanout, topic), lastpub */
                 if (s->lastpub) s->lastpub[(int64_t)p * s->t + t] = 0;
             } else {
-                const int n = get_peers(&h, gp->d, f_join, 0, P_JOIN, c);
+                const int n = get_peers(&h, gp->d, f_join, 0, P_JOIN, c, NULL);
                 for (int k = 0; k < n; ++k) s->tflags[ti(&h, c[k].e)] |= TF_MESH;
             }
             if (c != buf) free(c);
@@ -735,4 +760,27 @@ void orc_set_subscriptions(orc_net* s, const uint32_t* pairs, int32_t count, int
             }
         }
     }
+}
+
+/* ---- branch census and key access (oracle.h) ----------------------------- */
+
+int32_t orc_census_on;
+uint64_t orc_census_tab[ORC_CB_COUNT][ORC_CENSUS_CLASSES];
+
+void orc_census_enable(int on) { orc_census_on = on != 0; }
+
+void orc_census_reset(void) { memset(orc_census_tab, 0, sizeof orc_census_tab); }
+
+void orc_census_read(uint64_t* out) { memcpy(out, orc_census_tab, sizeof orc_census_tab); }
+
+uint64_t orc_select_key(uint64_t seed, uint64_t tick, uint32_t obs, int32_t topic, uint32_t purpose, uint32_t col,
+                        uint32_t pos)
+{
+    return okey(seed, tick, obs, topic, purpose, col, pos);
+}
+
+uint64_t orc_px_key(uint64_t seed, uint64_t tick, uint32_t obs, int32_t topic, uint32_t purpose, uint32_t col,
+                    uint32_t pruned_pos, uint32_t pos)
+{
+    return opx_key(opx_base(seed, tick, obs, topic, purpose, col), pruned_pos, pos);
 }

@@ -69,3 +69,39 @@ def synthetic_state(st, rng, now: int, p_mesh: float):
     st.estate[...] = _abi.ES_TRACKED | _abi.ES_CONNECTED
     st.expire[...] = 0
     st.backoff[...] = 0
+
+
+def planted(n, T_, base_seed, hubs, rng, base_cap, exact=False, dial=0.5):
+    """power_law(n, 8, 2.5, base_cap, i0=1) plus hub rows; exact: a hub's row
+    has exactly the given length (else at least: the base's edges add to it).
+    dial: the probability that the higher-numbered end of a connection
+    dialled it (0.5: either end; small: high-numbered peers hold few outbound
+    connections)."""
+    from gsim import graphs
+    from gsim.engine import Network
+    base = graphs.power_law(n, 8, 2.5, base_cap, seed=base_seed, n_topics=T_, i0=1)
+    src = base.owner()
+    u = [src[src < base.col].astype(np.int64)]
+    v = [base.col[src < base.col].astype(np.int64)]
+    hub_ids = [h for h, _ in hubs]
+    pool = np.setdiff1d(np.arange(n), hub_ids)
+    for hub, deg in hubs:
+        have = base.col[base.row_ptr[hub]:base.row_ptr[hub + 1]]
+        if exact:
+            cand = np.setdiff1d(pool, have)
+            others = rng.choice(cand, size=deg - len(have), replace=False)
+        else:
+            others = rng.choice(pool, size=deg, replace=False)
+        u.append(np.full(len(others), hub, np.int64))
+        v.append(others.astype(np.int64))
+    u, v = np.concatenate(u), np.concatenate(v)
+    a_, b_ = np.minimum(u, v), np.maximum(u, v)
+    key = np.unique(a_ * n + b_)
+    a_, b_ = key // n, key % n
+    flip = rng.random(len(a_)) < dial                   # who dialled
+    row_ptr, col, outbound = graphs._csr_from_pairs(n, np.where(flip, b_, a_), np.where(flip, a_, b_))
+    ip_ids = np.arange(n, dtype=np.uint32)
+    ip_ids[2:2000] = 2 + (np.arange(1998) // 25)          # sybil IPs shared by 25 peers each (hub neighbours among them)
+    net = Network(n, row_ptr, col, outbound, np.full(n, (1 << T_) - 1, dtype=np.uint64),
+                  np.arange(n + 1, dtype=np.uint32), ip_ids, int(ip_ids.max()) + 1)
+    return net

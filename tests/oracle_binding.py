@@ -140,6 +140,11 @@ def load():
             "orc_gater_throttled": (c_int64, [c_void_p]),
             "orc_gater_read": (None, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
             "orc_gater_uniform": (ctypes.c_double, [c_uint64, c_int64, c_uint32, c_uint32, c_uint32]),
+            "orc_census_enable": (None, [ctypes.c_int]),
+            "orc_census_reset": (None, []),
+            "orc_census_read": (None, [c_void_p]),
+            "orc_select_key": (c_uint64, [c_uint64, c_uint64, c_uint32, c_int32, c_uint32, c_uint32, c_uint32]),
+            "orc_px_key": (c_uint64, [c_uint64, c_uint64, c_uint32, c_int32, c_uint32, c_uint32, c_uint32, c_uint32]),
         }
         for name, (res, args) in sig.items():
             fn = getattr(lib, name)
@@ -307,6 +312,55 @@ class NetState:
         self.lastpub[...] = rd(_abi.F_LASTPUB, "lastpub")
         self.fan_topics[...] = rd(_abi.F_FANOUT_TOPICS, "fan_topics")
 
+
+# oracle.h ORC_CB_*: the branch census, [branch][row class] (the row classes: up
+# to 8 connections, 9-16, 17-32, ..., 4097-8192, over 8192)
+CENSUS_BRANCHES = ("neg_prune", "dlo_all", "dlo_trunc", "dhi_prune", "rot_pass1", "rot_pass2", "dout_graft",
+                   "opp_all", "opp_trunc", "gossip_all", "gossip_select", "gossip_fill", "gossip_two", "gossip_both",
+                   "gossip_zero", "fanout_topup", "px_full", "px_trunc_small", "px_trunc_big")
+CENSUS_CLASSES = 12
+
+
+def row_class(deg):
+    """The row class of rows of `deg` connections (array or int)."""
+    bounds = 8 << np.arange(CENSUS_CLASSES - 1)
+    return np.searchsorted(bounds, np.asarray(deg), side="left")
+
+
+class Census:
+    """Counts the oracle's branches while open; .table maps a branch name to
+    its events per row class."""
+
+    def __enter__(self):
+        lib = load()
+        lib.orc_census_reset()
+        lib.orc_census_enable(1)
+        self.table = None
+        return self
+
+    def read(self):
+        out = np.zeros((len(CENSUS_BRANCHES), CENSUS_CLASSES), dtype=np.uint64)
+        load().orc_census_read(out.ctypes.data_as(c_void_p))
+        self.table = {b: out[q].astype(np.int64) for q, b in enumerate(CENSUS_BRANCHES)}
+        return self.table
+
+    def __exit__(self, *exc):
+        self.read()
+        load().orc_census_enable(0)
+        return False
+
+
+def select_key(seed, tick, obs, topic, purpose, col, pos):
+    return int(load().orc_select_key(seed, tick, obs, topic, purpose, col, pos))
+
+
+def px_key(seed, tick, obs, topic, purpose, col, pruned_pos, pos):
+    return int(load().orc_px_key(seed, tick, obs, topic, purpose, col, pruned_pos, pos))
+
+
+# oracle_internal.h: the selection purposes the port tests restate
+P_GRAFT_DLO, P_PRUNE_SHUF1, P_PRUNE_SHUF2, P_GRAFT_DOUT, P_GRAFT_OPP, P_GOSSIP = 1, 2, 3, 4, 5, 6
+P_GOSSIP_FILL, P_GOSSIP_DUP, P_PX = 9, 10, 14
 
 UNSEEN = 0xFFFFFFFF
 ORC_BEHAVE_IGNORE_IWANT = 0x01   # oracle.h: never answers IWANT
