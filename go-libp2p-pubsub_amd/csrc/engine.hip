@@ -1293,6 +1293,7 @@ int gsim_destroy(gsim_handle* h)
     free_gater(h);
     free_deliver(h);
     trace_release(h);
+    scoretracer_release(h);
     report_release(h);
     peerreport_release(h);
     scorereport_release(h);
@@ -1360,6 +1361,7 @@ int gsim_load_graph(gsim_handle* h, int64_t n, const uint32_t* row_ptr, const ui
     free_gater(h);
     free_deliver(h);
     trace_release(h);
+    scoretracer_release(h);
     h->n = n;
     h->e = E;
     h->n_ips = n_ips;

@@ -467,6 +467,7 @@ struct PeerReport; // the peer delivery report's device scratch (peerreport.hip)
 struct ScoreReport; // the score report's device scratch and what-if tables (scorereport.hip)
 struct MeshPaths;   // the mesh path report's per-peer words and counters (meshpaths.hip)
 struct RelayReport; // the relay report's device scratch (relayreport.hip)
+struct ScoreTracer; // the score tracer's delivery records and batch scratch (scoretracer.hip)
 using MsgReport = struct ::gsim_msg_report;   // (the call gsim_msg_report hides the struct's name in C++)
 
 // The peer gater's device state as the delivery kernels see it (gater.hip;
@@ -610,6 +611,7 @@ struct gsim_handle {
     gsim::ScoreReport* sr = nullptr; // gsim_score_report scratch (scorereport.hip), allocated at the first call
     gsim::MeshPaths* mp = nullptr;   // gsim_mesh_paths scratch (meshpaths.hip), allocated at the first call; a new graph drops it
     gsim::RelayReport* rl = nullptr; // gsim_relay_report scratch (relayreport.hip), allocated at the first call
+    gsim::ScoreTracer* st = nullptr; // gsim_score_tracer_config (scoretracer.hip); a new graph drops it
 
     // owned peers / observer rows (all of them unless sharded)
     int64_t olo() const { return sh ? sh->own_lo : 0; }
@@ -799,6 +801,7 @@ int relay_finish(gsim_handle* h, struct gsim_relay_row* peers, uint64_t* cto, st
                  struct gsim_relay_msg_row* msgs);
 int64_t deliver_last_round_time(gsim_handle* h);   // time of the last round run (INT64_MAX: none yet)
 void trace_release(gsim_handle* h);   // trace.hip
+void scoretracer_release(gsim_handle* h);   // scoretracer.hip
 // round stages (deliver.hip; gsim_round runs them in order, a sharded group
 // exchanges between them, shard.hip)
 int deliver_round_prepare(gsim_handle* h, int64_t round);

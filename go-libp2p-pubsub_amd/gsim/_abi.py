@@ -103,6 +103,24 @@ TRACE_JOIN, TRACE_LEAVE = 9, 10
 TRACE_RECV_RPC, TRACE_SEND_RPC = 6, 7          # reason 0: a forwarded message, 1: an IWANT answer
 
 
+# gsim_score_event (include/gsim.h): kinds and RejectMessage reasons (tracer.go:28-38)
+EV_VALIDATE, EV_DELIVER, EV_REJECT, EV_DUPLICATE, EV_GRAFT, EV_PRUNE, EV_ADD_PENALTY = range(7)
+(REJECT_BLACKLISTED_PEER, REJECT_BLACKLISTED_SOURCE, REJECT_MISSING_SIGNATURE, REJECT_UNEXPECTED_SIGNATURE,
+ REJECT_UNEXPECTED_AUTH_INFO, REJECT_INVALID_SIGNATURE, REJECT_VALIDATION_QUEUE_FULL, REJECT_VALIDATION_THROTTLED,
+ REJECT_VALIDATION_FAILED, REJECT_VALIDATION_IGNORED, REJECT_SELF_ORIGIN) = range(11)
+
+
+class CScoreEvent(Structure):
+    """struct gsim_score_event (32 bytes): one RawTracer call on one observer's peerScore."""
+    _fields_ = [("mid", c_uint64), ("now_ns", c_int64), ("observer", c_uint32), ("peer", c_uint32),
+                ("arg", ctypes.c_uint16), ("topic", c_uint8), ("kind", c_uint8), ("_pad", c_uint8 * 4)]
+
+
+# numpy view of gsim_score_event
+SCORE_EVENT_DTYPE = [("mid", "<u8"), ("now_ns", "<i8"), ("observer", "<u4"), ("peer", "<u4"), ("arg", "<u2"),
+                     ("topic", "u1"), ("kind", "u1"), ("_pad", "u1", (4,))]
+
+
 # (name, restype, argtypes) for every symbol include/gsim.h declares.
 class CMsgConfig(Structure):
     _fields_ = [("ring", c_int32), ("rounds", c_int32), ("t0_ns", c_int64), ("heartbeat_ns", c_int64),
@@ -290,7 +308,7 @@ TOPIC_SNAPSHOT_DTYPE = [("time_in_mesh_ns", "<i8"), ("first_message_deliveries",
                         ("mesh_message_deliveries", "<f8"), ("invalid_message_deliveries", "<f8")]
 
 KERNEL_CLASSES = ["refresh_score", "score", "ip_colocation", "heartbeat", "control", "publish", "send",
-                  "commit", "accept", "gossip", "churn"]
+                  "commit", "accept", "gossip", "churn", "tracer_sort", "tracer_resolve", "tracer_apply"]
 BEHAVE_IGNORE_IWANT = 0x01
 
 # gsim_host_transport callbacks (include/gsim.h)
@@ -437,6 +455,11 @@ SIGNATURES = [
     ("gsim_px_connect", c_int32, [c_void_p, c_int64, c_void_p, c_int64, c_void_p]),
     ("gsim_trace_config", c_int32, [c_void_p, c_uint32, c_uint32, c_int64]),
     ("gsim_trace_read", c_int32, [c_void_p, c_void_p, c_int64, c_void_p]),
+    ("gsim_score_tracer_config", c_int32, [c_void_p, c_int64, c_int64, c_int64]),
+    ("gsim_score_tracer_events", c_int32, [c_void_p, c_void_p, c_int64]),
+    ("gsim_score_tracer_gc", c_int32, [c_void_p, c_int64]),
+    ("gsim_score_tracer_stats", c_int32, [c_void_p, c_void_p]),
+    ("gsim_score_tracer_settled", c_int32, [c_void_p, c_void_p]),
     ("gsim_set_direct_peers", c_int32, [c_void_p, c_void_p]),
     ("gsim_profile", c_int32, [c_void_p, c_int32]),
     ("gsim_profile_read", c_int32, [c_void_p, c_void_p, c_void_p, c_int32]),

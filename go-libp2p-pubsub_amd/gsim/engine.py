@@ -407,6 +407,41 @@ class Engine:
         self._check(self.lib.gsim_trace_read(self.h, _ptr(out) if n.value else None, n.value, ctypes.byref(n)))
         return out[:n.value]
 
+    # -- score tracer events (gsim.tracer builds the arrays) ----------------------
+    def tracer_config(self, records_cap: int, peers_cap: int, seen_ttl: int = 0):
+        """Size the delivery records behind tracer_events: records_cap records
+        (one per (observer, message id) alive at a time), peers_cap entries of
+        their peers lists, seen_ttl ns of lifetime (0: TimeCacheDuration)
+        (gsim_score_tracer_config).  Calling it again drops every record."""
+        self._check(self.lib.gsim_score_tracer_config(self.h, int(records_cap), int(peers_cap), int(seen_ttl)))
+
+    def tracer_events(self, events: np.ndarray):
+        """Apply a batch of RawTracer calls (an array of gsim.tracer.EVENT_DTYPE;
+        the builders of gsim.tracer make its rows): each observer's events in
+        array order, observers independently (gsim_score_tracer_events).  A bad
+        event fails the whole batch (ValueError naming its index, nothing
+        applied); a batch the record space may not hold is a GsimError
+        (GSIM_ERANGE, nothing applied)."""
+        a = np.ascontiguousarray(events, dtype=np.dtype(_abi.SCORE_EVENT_DTYPE))
+        self._check(self.lib.gsim_score_tracer_events(self.h, _ptr(a) if len(a) else None, len(a)))
+
+    def tracer_gc(self, now: int):
+        """gcDeliveryRecords (score.go:863-877): drop the records with now > expire (gsim_score_tracer_gc)."""
+        self._check(self.lib.gsim_score_tracer_gc(self.h, int(now)))
+
+    def tracer_stats(self) -> dict:
+        """Live records, live peers-list entries, events applied, records collected (gsim_score_tracer_stats)."""
+        out = np.zeros(4, dtype=np.int64)
+        self._check(self.lib.gsim_score_tracer_stats(self.h, _ptr(out)))
+        return dict(zip(["records", "peer_entries", "events", "collected"], (int(x) for x in out)))
+
+    def tracer_settled(self) -> tuple:
+        """(records whose pending mesh-delivery increments an event settled so
+        far, whether the engine still holds such increments) (gsim_score_tracer_settled)."""
+        out = np.zeros(2, dtype=np.int64)
+        self._check(self.lib.gsim_score_tracer_settled(self.h, _ptr(out)))
+        return int(out[0]), bool(out[1])
+
     def set_direct_peers(self, flags):
         """WithDirectPeers as per-edge flags (edge order; None clears)
         (gsim_set_direct_peers; gossipsub.go:352-374)."""

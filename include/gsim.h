@@ -928,6 +928,96 @@ int gsim_trace_config(gsim_handle* h, uint32_t peer_lo, uint32_t peer_hi, int64_
  * overflowed). */
 int gsim_trace_read(gsim_handle* h, gsim_trace_event* out, int64_t cap, int64_t* n);
 
+/* ---- score tracer events: peerScore's RawTracer surface from outside ------
+ * (trace.go:27-60, score.go:88; SURVEY.md §8(b) part 2).  A caller that owns
+ * the routers -- an event-driven simulator, a replay of a TraceEvent stream, a
+ * Go router bound through cgo -- hands the calls its routers' score tracers
+ * would receive to the engine in batches; the engine keeps every router's
+ * peerStats and delivery records (score.go:90-120) and scores as usual.
+ *
+ * Ordering: the events of one observer take effect in array order; observers
+ * are independent (an observer's events touch only its own records about its
+ * neighbours and its own delivery records), so the result does not depend on
+ * how observers interleave in the array, which need not be grouped or sorted.
+ *
+ * Each event is the RawTracer method of its kind on the observer's peerScore,
+ * as the CPU oracle restates it (oracle/oracle.c).  Changed: first / meshd /
+ * fail / invalid / graft / meshTime, the score bits of GSIM_F_TFLAGS, and bp.
+ * Router state (mesh flags, connections, backoff, the control inbox) is not
+ * touched, nor are the peer gater, the IWANT promises and the trace export.
+ * Connections still change through gsim_set_connections (AddPeer /
+ * RemovePeer).  A peer without peerStats and a topic without score parameters
+ * are the reference's silent returns (the delivery record is still updated). */
+#define GSIM_EV_VALIDATE    0   /* ValidateMessage   score.go:693-700 */
+#define GSIM_EV_DELIVER     1   /* DeliverMessage    score.go:702-726 */
+#define GSIM_EV_REJECT      2   /* RejectMessage     score.go:728-793, arg = GSIM_REJECT_* */
+#define GSIM_EV_DUPLICATE   3   /* DuplicateMessage  score.go:795-827 */
+#define GSIM_EV_GRAFT       4   /* Graft             score.go:649-667 */
+#define GSIM_EV_PRUNE       5   /* Prune             score.go:669-691 */
+#define GSIM_EV_ADD_PENALTY 6   /* AddPenalty        score.go:391-405, arg = count */
+/* RejectMessage reasons, in the order of tracer.go:28-38 */
+#define GSIM_REJECT_BLACKLISTED_PEER      0
+#define GSIM_REJECT_BLACKLISTED_SOURCE    1
+#define GSIM_REJECT_MISSING_SIGNATURE     2
+#define GSIM_REJECT_UNEXPECTED_SIGNATURE  3
+#define GSIM_REJECT_UNEXPECTED_AUTH_INFO  4
+#define GSIM_REJECT_INVALID_SIGNATURE     5
+#define GSIM_REJECT_VALIDATION_QUEUE_FULL 6
+#define GSIM_REJECT_VALIDATION_THROTTLED  7
+#define GSIM_REJECT_VALIDATION_FAILED     8
+#define GSIM_REJECT_VALIDATION_IGNORED    9
+#define GSIM_REJECT_SELF_ORIGIN           10
+
+typedef struct gsim_score_event {   /* 32 bytes */
+    uint64_t mid;        /* message id (message events) */
+    int64_t  now_ns;     /* time.Now() as the tracer saw it */
+    uint32_t observer;   /* the router whose peerScore receives the call */
+    uint32_t peer;       /* msg.ReceivedFrom / the grafted, pruned, penalised peer */
+    uint16_t arg;        /* reject reason / penalty count */
+    uint8_t  topic, kind;
+    uint8_t  _pad[4];
+} gsim_score_event;
+
+/* Size the delivery records: room for records_cap records (one per (observer,
+ * message id) alive at a time) and peers_cap entries of their peers lists
+ * (deliveryRecord.peers); seen_ttl_ns is the records' lifetime (0:
+ * TimeCacheDuration, 120 s).  Calling it again drops every record.  Needs a
+ * graph (GSIM_ESTATE); a new graph drops the configuration.  A shard of a
+ * group: GSIM_ESTATE (as the three calls below). */
+int gsim_score_tracer_config(gsim_handle* h, int64_t records_cap, int64_t peers_cap, int64_t seen_ttl_ns);
+
+/* Apply n events.  The whole batch is checked first: GSIM_EINVAL, with the
+ * first offending index in gsim_last_error and nothing applied, on an unknown
+ * kind, a reject reason above 10, an observer or peer >= N, a peer that is no
+ * connection (CSR neighbour) of the observer, a topic >= T or one the observer
+ * has not announced (every kind but ADD_PENALTY, which has no topic), or a
+ * time that goes backwards for an observer (within the batch or against its
+ * last event of an earlier batch).  GSIM_ERANGE, nothing applied, when the
+ * batch could need more records or peers-list entries than are free: one
+ * record per event that reaches getRecord (VALIDATE, DELIVER, DUPLICATE,
+ * REJECT with a validation reason 7-9), one entry per DUPLICATE.  Entries of a
+ * released list (RejectMessage) are free again after the next
+ * gsim_score_tracer_gc.  GSIM_ESTATE before gsim_score_tracer_config.
+ * Synchronizes. */
+int gsim_score_tracer_events(gsim_handle* h, const gsim_score_event* ev, int64_t n);
+
+/* gcDeliveryRecords (score.go:587-592, 863-877): drop every record with
+ * now_ns > expire (strict); their space is reusable afterwards, and an id seen
+ * again is a fresh record.  Per-observer times are non-decreasing and the TTL
+ * is one constant, so expiry order is creation order: exactly the records the
+ * reference's queue-head loop drops.  Synchronizes. */
+int gsim_score_tracer_gc(gsim_handle* h, int64_t now_ns);
+
+/* out4 = {live records, live peers-list entries, events applied, records
+ * collected} since gsim_score_tracer_config. */
+int gsim_score_tracer_stats(gsim_handle* h, int64_t* out4);
+
+/* Diagnostic: out2 = {score records whose pending meshMessageDeliveries
+ * increments (left by simulated rounds, not yet folded into the counter) an
+ * event settled before it read or changed the counter, since
+ * gsim_score_tracer_config; 1 while the engine holds such increments}. */
+int gsim_score_tracer_settled(gsim_handle* h, int64_t* out2);
+
 /* Copy the score snapshot (E doubles, edge order) to host. */
 int gsim_read_scores(gsim_handle* h, double* out);
 
@@ -1024,6 +1114,9 @@ typedef enum gsim_kernel_class {
     GSIM_K_ACCEPT,             /* AcceptFrom verdicts from a new score snapshot */
     GSIM_K_GOSSIP,             /* handleIHave/handleIWant + IWANT response delivery */
     GSIM_K_CHURN,              /* AddPeer/RemovePeer of gsim_set_connections */
+    GSIM_K_TRACER_SORT,        /* gsim_score_tracer_events: grouping the batch by observer */
+    GSIM_K_TRACER_RESOLVE,     /* ... the events' edges and the batch checks */
+    GSIM_K_TRACER_APPLY,       /* ... the per-observer walk over the events */
     GSIM_K__COUNT
 } gsim_kernel_class;
 /* Enable (1) or disable (0) recording; clears recorded totals. */
