@@ -217,6 +217,8 @@ struct Deliver {
     int64_t resp_round = -1;           // round in which the queued responses arrive
 };
 
+constexpr uint32_t kMcntSpill = 128;    // pending mesh-delivery increments a record's byte holds (atomic_mcnt_inc)
+
 struct RoundArgs {
     int64_t N, E;
     int32_t T, ring, R;
@@ -1646,12 +1648,14 @@ void k_send_tm(RoundArgs a_)
                                 inv_mark(a);
                             } else if (!inv && (tf & GSIM_TF_IN_MESH)) {
                                 if (inw[u]) {
-                                    uint32_t n = nv[u];
-                                    if (n == 255u) {
+                                    // the byte stays under kMcntSpill between launches: a later
+                                    // launch's atomic_mcnt_inc must have room for its copies
+                                    uint32_t n = nv[u] + 1u;
+                                    if (n >= kMcntSpill) {
                                         a.meshd[ir] = apply_incs(a.meshd[ir], n, mcap);
                                         n = 0;
                                     }
-                                    a.mcnt[ir] = (uint8_t)(n + 1);
+                                    a.mcnt[ir] = (uint8_t)n;
                                 }
                             }
                         }
@@ -2904,13 +2908,16 @@ __global__ __launch_bounds__(256) void k_promise_insert(uint64_t* pcand, uint32_
     }
 }
 
-// One pending meshMessageDeliveries increment of record ir: a byte add on
-// the containing word; the add that makes kMcntSpill pending moves them to
-// meshd.  Increments are x -> min(x + 1, cap) one after the other until the
-// next refresh applies the rest, so how they are grouped into spills does not
-// change the result; fewer than 256 - kMcntSpill copies of one record arrive
-// in one launch, so the byte never carries into its neighbour.
-constexpr uint32_t kMcntSpill = 128;
+// One pending meshMessageDeliveries increment of record ir, on its byte of
+// the containing word; the copy that would leave kMcntSpill or more pending
+// takes kMcntSpill of them out in the same exchange and moves them to meshd.
+// Increments are x -> min(x + 1, cap) one after the other until the next
+// refresh applies the rest, so how they are grouped into spills does not
+// change the result.  A compare-and-swap on the word, not a byte add with the
+// spill after it: any number of copies of one record may arrive in one launch
+// (a hub answering one peer's IWANT for hundreds of messages), and an add
+// that ran ahead of its spill carried into the neighbouring record's byte.
+// The byte may come in over kMcntSpill already (the bounded adds stop at 200).
 constexpr int kPubTicks = 16;      // publication window of the mcnt_fast bound (>= HistoryLength + 3)
 __device__ __forceinline__ void atomic_mcnt_inc(uint8_t* mcnt, int64_t ir, double* meshd, double cap, bool fast = false)
 {
@@ -2920,9 +2927,17 @@ __device__ __forceinline__ void atomic_mcnt_inc(uint8_t* mcnt, int64_t ir, doubl
         __hip_atomic_fetch_add(w, 1u << sh, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         return;
     }
-    const uint32_t old = atomicAdd(w, 1u << sh);
-    if (((old >> sh) & 0xFFu) != kMcntSpill - 1u) return;
-    atomicSub(w, kMcntSpill << sh);
+    uint32_t ow = __hip_atomic_load(w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    bool spill;
+    for (;;) {
+        const uint32_t nb = ((ow >> sh) & 0xFFu) + 1u;
+        spill = nb >= kMcntSpill;
+        const uint32_t nw = (ow & ~(0xFFu << sh)) | ((spill ? nb - kMcntSpill : nb) << sh);
+        const uint32_t pw = atomicCAS(w, ow, nw);
+        if (pw == ow) break;
+        ow = pw;
+    }
+    if (!spill) return;
     unsigned long long* q = reinterpret_cast<unsigned long long*>(meshd);
     unsigned long long o = __hip_atomic_load(q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     for (;;) {

@@ -6,7 +6,7 @@
  * Compiled with -ffp-contract=off so every fp64 operation rounds exactly as the
  * reference's Go code (Go never fuses a*b+c into an FMA on amd64).
  */
-#include "oracle.h"
+#include "oracle_internal.h"
 
 #include <stdlib.h>
 #include <string.h>
@@ -21,6 +21,59 @@
 
 static inline int64_t te(const orc_net* s, int32_t t, int64_t e) { return (int64_t)t * s->e + e; }
 
+/* ---- score-branch census (oracle.h ORC_SB_*) ------------------------------ */
+int32_t orc_sb_on;
+uint64_t orc_sb_tab[ORC_SB_COUNT];
+static uint32_t* sb_pend;            /* [T][E] mesh credits of a record since the last refresh */
+static int64_t sb_pend_n;
+
+void orc_score_census_enable(int on) { orc_sb_on = on != 0; }
+
+void orc_score_census_reset(void)
+{
+    memset(orc_sb_tab, 0, sizeof orc_sb_tab);
+    free(sb_pend);
+    sb_pend = NULL;
+    sb_pend_n = 0;
+}
+
+void orc_score_census_read(uint64_t* out) { memcpy(out, orc_sb_tab, sizeof orc_sb_tab); }
+
+/* serial: called at the start of orc_refresh_scores */
+void orc_sb_pending_reset(const orc_net* s)
+{
+    if (!orc_sb_on) return;
+    const int64_t n = (int64_t)s->t * s->e;
+    if (n != sb_pend_n) {
+        free(sb_pend);
+        sb_pend = (uint32_t*)malloc(sizeof(uint32_t) * (size_t)(n > 0 ? n : 1));
+        sb_pend_n = sb_pend ? n : 0;
+    }
+    if (sb_pend) memset(sb_pend, 0, sizeof(uint32_t) * (size_t)sb_pend_n);
+}
+
+uint32_t orc_sb_pending(const orc_net* s, int64_t i)
+{
+    return (orc_sb_on && sb_pend && (int64_t)s->t * s->e == sb_pend_n) ? sb_pend[i] : 0;
+}
+
+/* a record is credited by its observer's thread alone; the maximum is shared */
+void orc_sb_pending_inc(const orc_net* s, int64_t i)
+{
+    if (!orc_sb_on || !sb_pend || (int64_t)s->t * s->e != sb_pend_n) return;
+    const uint64_t c = ++sb_pend[i];
+#pragma omp critical(orc_sb_max)
+    if (c > orc_sb_tab[ORC_SB_MESH_PENDING_MAX]) orc_sb_tab[ORC_SB_MESH_PENDING_MAX] = c;
+}
+
+/* one decay: ZERO when a non-zero counter snaps, EDGE when the product is DecayToZero exactly */
+static inline void sb_decay(int base, double before, double x, double dtz)
+{
+    if (!orc_sb_on) return;
+    if (x < dtz) { if (before != 0.0) orc_sb(base); }
+    else if (x == dtz) orc_sb(base + 1);
+}
+
 /* ------------------------------------------------------------------------ */
 /* score.go:504-565 refreshScores.  Disconnected peers past their retention are
  * purged (score.go:510-523); retained ones are not decayed.  Connected peers:
@@ -31,12 +84,15 @@ void orc_refresh_scores(orc_net* s, int64_t now)
 {
     const gsim_peer_score_params* pp = s->pp;
     const double dtz = pp->decay_to_zero;
+    orc_sb_pending_reset(s);
     /* edges are independent: the OpenMP split gives identical results */
 #pragma omp parallel for schedule(static)
     for (int64_t e = 0; e < s->e; ++e) {
         uint8_t st = s->estate[e];
         if (!(st & ES_TRACKED)) continue;
         if (!(st & ES_CONN)) {
+            if (orc_sb_on) orc_sb(now > s->expire[e] ? ORC_SB_RETAIN_PURGED : now == s->expire[e] ? ORC_SB_RETAIN_EDGE
+                                                                                                  : ORC_SB_RETAIN_SKIPPED);
             if (now > s->expire[e]) {                 /* now.After(pstats.expire) */
                 s->estate[e] = 0;                     /* delete(ps.peerStats, p) */
                 s->bp[e] = 0.0;
@@ -56,20 +112,28 @@ void orc_refresh_scores(orc_net* s, int64_t now)
             int64_t i = te(s, t, e);
             double x;
             x = s->first[i] * tp->first_message_deliveries_decay;
+            sb_decay(ORC_SB_DECAY_FIRST_ZERO, s->first[i], x, dtz);
             if (x < dtz) x = 0.0;
             s->first[i] = x;
             x = s->meshd[i] * tp->mesh_message_deliveries_decay;
+            sb_decay(ORC_SB_DECAY_MESHD_ZERO, s->meshd[i], x, dtz);
             if (x < dtz) x = 0.0;
             s->meshd[i] = x;
             x = s->fail[i] * tp->mesh_failure_penalty_decay;
+            sb_decay(ORC_SB_DECAY_FAIL_ZERO, s->fail[i], x, dtz);
             if (x < dtz) x = 0.0;
             s->fail[i] = x;
             x = s->invalid[i] * tp->invalid_message_deliveries_decay;
+            sb_decay(ORC_SB_DECAY_INVALID_ZERO, s->invalid[i], x, dtz);
             if (x < dtz) x = 0.0;
             s->invalid[i] = x;
             if (s->tflags[i] & TF_IN_MESH) {
                 int64_t mt = now - s->graft_time[i];  /* now.Sub(tstats.graftTime) */
                 s->mesh_time[i] = mt;
+                if (orc_sb_on && !(s->tflags[i] & TF_ACTIVE)) {
+                    if (mt > tp->mesh_message_deliveries_activation_ns) orc_sb(ORC_SB_ACT_SET);
+                    else if (mt == tp->mesh_message_deliveries_activation_ns) orc_sb(ORC_SB_ACT_EDGE);
+                }
                 if (mt > tp->mesh_message_deliveries_activation_ns) s->tflags[i] |= TF_ACTIVE;
             } else {
                 /* meshTime of a record outside the mesh is never read (score.go:286,
@@ -79,6 +143,7 @@ void orc_refresh_scores(orc_net* s, int64_t now)
             }
         }
         double b = s->bp[e] * pp->behaviour_penalty_decay;
+        sb_decay(ORC_SB_DECAY_BP_ZERO, s->bp[e], b, dtz);
         if (b < dtz) b = 0.0;
         s->bp[e] = b;
     }
@@ -87,14 +152,17 @@ void orc_refresh_scores(orc_net* s, int64_t now)
 /* score.go:265-342 score(p): per-topic P1..P4 accumulated in ascending topic
  * order, mixed with TopicWeight, capped by TopicScoreCap,
  * then P5, P6, P7. */
-double orc_score_edge(const orc_net* s, int64_t e)
+static double score_edge(const orc_net* s, int64_t e, const int sb)
 {
     if (!(s->estate[e] & ES_TRACKED)) return 0.0;     /* !ok -> 0 */
     const gsim_peer_score_params* pp = s->pp;
     double score = 0.0;
     for (int32_t t = 0; t < s->t; ++t) {
         const gsim_topic_score_params* tp = &s->tp[t];
-        if (!tp->scored) continue;
+        if (!tp->scored) {
+            if (sb) orc_sb(ORC_SB_UNSCORED_SKIPPED);
+            continue;
+        }
         int64_t i = te(s, t, e);
         uint8_t f = s->tflags[i];
         double ts = 0.0;
@@ -102,27 +170,39 @@ double orc_score_edge(const orc_net* s, int64_t e)
             double p1 = 0.0;
             if (tp->time_in_mesh_quantum_ns != 0)      /* Go would panic on /0 */
                 p1 = (double)(s->mesh_time[i] / tp->time_in_mesh_quantum_ns);
+            if (sb) orc_sb(p1 < 0 ? ORC_SB_P1_NEGATIVE : p1 > tp->time_in_mesh_cap ? ORC_SB_P1_CAPPED
+                           : p1 == tp->time_in_mesh_cap ? ORC_SB_P1_AT_CAP : ORC_SB_P1_UNCAPPED);
             if (p1 > tp->time_in_mesh_cap) p1 = tp->time_in_mesh_cap;
             ts += p1 * tp->time_in_mesh_weight;
         }
         ts += s->first[i] * tp->first_message_deliveries_weight;       /* P2 */
         if (f & TF_ACTIVE) {                                           /* P3 */
             double md = s->meshd[i];
+            if (sb && md <= tp->mesh_message_deliveries_threshold)
+                orc_sb(md < tp->mesh_message_deliveries_threshold ? ORC_SB_P3_DEFICIT : ORC_SB_P3_AT_THRESHOLD);
             if (md < tp->mesh_message_deliveries_threshold) {
                 double deficit = tp->mesh_message_deliveries_threshold - md;
                 double p3 = deficit * deficit;
                 ts += p3 * tp->mesh_message_deliveries_weight;
             }
         }
+        else if (sb && (f & TF_IN_MESH)) orc_sb(ORC_SB_P3_INACTIVE);
         ts += s->fail[i] * tp->mesh_failure_penalty_weight;            /* P3b */
         double p4 = s->invalid[i] * s->invalid[i];                     /* P4 */
         ts += p4 * tp->invalid_message_deliveries_weight;
         score += ts * tp->topic_weight;
     }
+    if (sb && pp->topic_score_cap > 0) {
+        if (score > pp->topic_score_cap) orc_sb(ORC_SB_TSC_APPLIED);
+        else if (score == pp->topic_score_cap) orc_sb(ORC_SB_TSC_AT_CAP);
+        else if (score < 0) orc_sb(ORC_SB_TSC_NEGATIVE);
+    }
     if (pp->topic_score_cap > 0 && score > pp->topic_score_cap) score = pp->topic_score_cap;
     double p5 = s->p5 ? s->p5[s->col[e]] : 0.0;                        /* P5 */
     score += p5 * pp->app_specific_weight;
     score += s->p6[e] * pp->ip_colocation_factor_weight;               /* P6 */
+    if (sb && s->bp[e] != 0.0 && s->bp[e] >= pp->behaviour_penalty_threshold)
+        orc_sb(s->bp[e] > pp->behaviour_penalty_threshold ? ORC_SB_P7_EXCESS : ORC_SB_P7_AT_THRESHOLD);
     if (s->bp[e] > pp->behaviour_penalty_threshold) {                  /* P7 */
         double excess = s->bp[e] - pp->behaviour_penalty_threshold;
         double p7 = excess * excess;
@@ -130,6 +210,8 @@ double orc_score_edge(const orc_net* s, int64_t e)
     }
     return score;
 }
+
+double orc_score_edge(const orc_net* s, int64_t e) { return score_edge(s, e, 0); }
 
 /* OpenMP threads of the parallel phases (the CPU baseline's single-core and
  * all-core legs); returns the number in effect (1 without OpenMP) */
@@ -147,7 +229,7 @@ int orc_set_threads(int n)
 void orc_compute_scores(orc_net* s)
 {
 #pragma omp parallel for schedule(static)
-    for (int64_t e = 0; e < s->e; ++e) s->score[e] = orc_score_edge(s, e);
+    for (int64_t e = 0; e < s->e; ++e) s->score[e] = score_edge(s, e, orc_sb_on);
 }
 
 /* score.go:344-388 ipColocationFactor.  peersInIP = len(ps.peerIPs[ip]) counts
@@ -163,9 +245,13 @@ void orc_ip_colocation(orc_net* s)
             double res = 0.0;
             if (s->estate[e] & ES_TRACKED) {
                 uint32_t j = s->col[e];
+                if (s->ip_ptr[j + 1] - s->ip_ptr[j] > 1) orc_sb(ORC_SB_P6_MULTI_IP);
                 for (uint32_t q = s->ip_ptr[j]; q < s->ip_ptr[j + 1]; ++q) {
                     uint32_t ip = s->ip_ids[q];
-                    if (s->ip_white && s->ip_white[ip]) continue;   /* whitelisted */
+                    if (s->ip_white && s->ip_white[ip]) {            /* whitelisted */
+                        orc_sb(ORC_SB_P6_WHITELISTED);
+                        continue;
+                    }
                     int32_t cnt = 0;
                     for (uint32_t e2 = b; e2 < en; ++e2) {
                         if (!(s->estate[e2] & ES_TRACKED)) continue;
@@ -173,6 +259,7 @@ void orc_ip_colocation(orc_net* s)
                         for (uint32_t q2 = s->ip_ptr[j2]; q2 < s->ip_ptr[j2 + 1]; ++q2)
                             if (s->ip_ids[q2] == ip) { ++cnt; break; }
                     }
+                    if (cnt >= thr) orc_sb(cnt > thr ? ORC_SB_P6_SURPLUS : ORC_SB_P6_AT_THRESHOLD);
                     if (cnt > thr) {
                         double surplus = (double)(cnt - thr);
                         res += surplus * surplus;
@@ -211,6 +298,10 @@ void orc_prune(orc_net* s, int64_t e, int32_t topic)
     if (!s->tp[topic].scored) return;
     int64_t i = te(s, topic, e);
     double thr = s->tp[topic].mesh_message_deliveries_threshold;
+    if (orc_sb_on) {
+        orc_sb(((s->tflags[i] & TF_ACTIVE) && s->meshd[i] < thr) ? ORC_SB_PRUNE_DEFICIT : ORC_SB_PRUNE_NO_DEFICIT);
+        if (orc_sb_pending(s, i)) orc_sb(ORC_SB_PRUNE_PENDING);
+    }
     if ((s->tflags[i] & TF_ACTIVE) && s->meshd[i] < thr) {
         double deficit = thr - s->meshd[i];
         s->fail[i] += deficit * deficit;
@@ -295,6 +386,13 @@ void orc_mark_invalid(orc_net* s, int64_t e, int32_t topic)
     s->invalid[te(s, topic, e)] += 1;
 }
 
+/* a credit of 1 against its cap: base + 0 stays below, + 1 reaches it, + 2 was there already */
+static inline void sb_credit(int base, double before, double cap)
+{
+    if (!orc_sb_on) return;
+    orc_sb(base + (before >= cap ? 2 : before + 1 >= cap ? 1 : 0));
+}
+
 /* score.go:919-946 */
 void orc_mark_first(orc_net* s, int64_t e, int32_t topic)
 {
@@ -302,10 +400,13 @@ void orc_mark_first(orc_net* s, int64_t e, int32_t topic)
     const gsim_topic_score_params* tp = &s->tp[topic];
     int64_t i = te(s, topic, e);
     double x = s->first[i] + 1;
+    sb_credit(ORC_SB_FIRST_BELOW, s->first[i], tp->first_message_deliveries_cap);
     if (x > tp->first_message_deliveries_cap) x = tp->first_message_deliveries_cap;
     s->first[i] = x;
     if (!(s->tflags[i] & TF_IN_MESH)) return;
     x = s->meshd[i] + 1;
+    sb_credit(ORC_SB_MESH_BELOW, s->meshd[i], tp->mesh_message_deliveries_cap);
+    orc_sb_pending_inc(s, i);
     if (x > tp->mesh_message_deliveries_cap) x = tp->mesh_message_deliveries_cap;
     s->meshd[i] = x;
 }
@@ -318,8 +419,14 @@ void orc_mark_duplicate(orc_net* s, int64_t e, int32_t topic, int32_t has_valida
     int64_t i = te(s, topic, e);
     if (!(s->tflags[i] & TF_IN_MESH)) return;
     const gsim_topic_score_params* tp = &s->tp[topic];
+    if (orc_sb_on && has_validated) {
+        const int64_t dt = now - validated, w = tp->mesh_message_deliveries_window_ns;
+        orc_sb(dt > w ? ORC_SB_WIN_OUTSIDE : dt == w ? ORC_SB_WIN_EDGE : ORC_SB_WIN_INSIDE);
+    }
     if (has_validated && (now - validated) > tp->mesh_message_deliveries_window_ns) return;
     double x = s->meshd[i] + 1;
+    sb_credit(ORC_SB_MESH_BELOW, s->meshd[i], tp->mesh_message_deliveries_cap);
+    orc_sb_pending_inc(s, i);
     if (x > tp->mesh_message_deliveries_cap) x = tp->mesh_message_deliveries_cap;
     s->meshd[i] = x;
 }

@@ -269,6 +269,82 @@ void orc_census_enable(int on);
 void orc_census_reset(void);
 void orc_census_read(uint64_t* out);     /* [ORC_CB_COUNT][ORC_CENSUS_CLASSES] */
 
+/* ---- score-branch census ------------------------------------------------- */
+/* The same for the scoring, credit and threshold code: one flat table of
+ * events, counted while orc_score_census_enable(1) holds (off by default: one
+ * test of a flag per event; updates are atomic).  "exactly at" events are the
+ * ones that tell `<` from `<=`.  The score() events are counted by
+ * orc_compute_scores alone (once per record and tick), not by the live
+ * Score(p) calls of emitGossip, Join and RemovePeer. */
+enum {
+    /* score.go:286-292 P1 (the quotient is Go's truncating integer division) */
+    ORC_SB_P1_UNCAPPED = 0,  /* 0 <= quotient < TimeInMeshCap */
+    ORC_SB_P1_CAPPED,        /* quotient > cap */
+    ORC_SB_P1_AT_CAP,        /* quotient == cap: either spelling gives the cap */
+    ORC_SB_P1_NEGATIVE,      /* meshTime < 0 (a graft time after the clock) */
+    /* score.go:550-556 activation */
+    ORC_SB_ACT_SET,          /* meshTime > Activation for the first time: set in this pass */
+    ORC_SB_ACT_EDGE,         /* meshTime == Activation exactly: not yet active */
+    /* score.go:300-307 P3 */
+    ORC_SB_P3_DEFICIT,       /* active and meshd < Threshold */
+    ORC_SB_P3_AT_THRESHOLD,  /* active and meshd == Threshold exactly: no deficit */
+    ORC_SB_P3_INACTIVE,      /* in the mesh, not active: P3 not looked at */
+    /* score.go:669-691 Prune */
+    ORC_SB_PRUNE_DEFICIT,    /* active with a deficit: the sticky penalty added */
+    ORC_SB_PRUNE_NO_DEFICIT, /* inactive, or meshd >= Threshold */
+    ORC_SB_PRUNE_PENDING,    /* the record took mesh credits earlier in the same tick */
+    /* score.go:919-946 markFirstMessageDelivery, 951-981 markDuplicateMessageDelivery */
+    ORC_SB_FIRST_BELOW,      /* first + 1 < FirstMessageDeliveriesCap */
+    ORC_SB_FIRST_REACH,      /* first < cap <= first + 1: this credit reaches the cap */
+    ORC_SB_FIRST_AT,         /* first >= cap already */
+    ORC_SB_MESH_BELOW,       /* the same three for a mesh credit (either function) */
+    ORC_SB_MESH_REACH,
+    ORC_SB_MESH_AT,
+    ORC_SB_MESH_PENDING_MAX, /* not a count: the most mesh credits one record took within one tick
+                                (between two orc_refresh_scores) */
+    /* score.go:533-549 the four decays (and P7's, 559-563) */
+    ORC_SB_DECAY_FIRST_ZERO, ORC_SB_DECAY_FIRST_EDGE,     /* ZERO: a non-zero counter snapped to 0 */
+    ORC_SB_DECAY_MESHD_ZERO, ORC_SB_DECAY_MESHD_EDGE,     /* EDGE: the product == DecayToZero exactly: kept */
+    ORC_SB_DECAY_FAIL_ZERO, ORC_SB_DECAY_FAIL_EDGE,
+    ORC_SB_DECAY_INVALID_ZERO, ORC_SB_DECAY_INVALID_EDGE,
+    ORC_SB_DECAY_BP_ZERO, ORC_SB_DECAY_BP_EDGE,
+    /* score.go:321-324 TopicScoreCap */
+    ORC_SB_TSC_APPLIED,      /* cap > 0 and sum > cap */
+    ORC_SB_TSC_AT_CAP,       /* cap > 0 and sum == cap exactly */
+    ORC_SB_TSC_NEGATIVE,     /* cap > 0 and sum < 0: left alone */
+    /* score.go:344-388 ipColocationFactor */
+    ORC_SB_P6_SURPLUS,       /* per (record, IP): peersInIP > threshold */
+    ORC_SB_P6_AT_THRESHOLD,  /* peersInIP == threshold exactly: no surplus */
+    ORC_SB_P6_WHITELISTED,   /* the IP is whitelisted: skipped */
+    ORC_SB_P6_MULTI_IP,      /* per record: the peer has several IPs */
+    /* score.go:333-338 P7 */
+    ORC_SB_P7_EXCESS,        /* bp > BehaviourPenaltyThreshold */
+    ORC_SB_P7_AT_THRESHOLD,  /* bp == threshold exactly (and not 0): no excess */
+    /* score.go:510-523 retention */
+    ORC_SB_RETAIN_PURGED,    /* now > expire */
+    ORC_SB_RETAIN_EDGE,      /* now == expire exactly: kept */
+    ORC_SB_RETAIN_SKIPPED,   /* retained and not yet due: not decayed */
+    /* score.go:970-975 the duplicate window (validated copies of mesh peers) */
+    ORC_SB_WIN_INSIDE,       /* now - validated < window */
+    ORC_SB_WIN_OUTSIDE,      /* > window: no credit */
+    ORC_SB_WIN_EDGE,         /* == window exactly: credited */
+    /* the five thresholds: score < threshold, score > threshold, score == threshold.
+     * gossip: gossipsub.go:659-663 (handleIHave), 699-703 (handleIWant), 1729-1731 (emitGossip);
+     * publish: 991-995 (flood publish), 1571-1584 (fanout upkeep); graylist: 598-609 (AcceptFrom);
+     * accept-PX: 852-858 (handlePrune); opportunistic graft: 1535-1538 (the median) */
+    ORC_SB_TH_GOSSIP_BELOW, ORC_SB_TH_GOSSIP_ABOVE, ORC_SB_TH_GOSSIP_EQUAL,
+    ORC_SB_TH_PUBLISH_BELOW, ORC_SB_TH_PUBLISH_ABOVE, ORC_SB_TH_PUBLISH_EQUAL,
+    ORC_SB_TH_GRAYLIST_BELOW, ORC_SB_TH_GRAYLIST_ABOVE, ORC_SB_TH_GRAYLIST_EQUAL,
+    ORC_SB_TH_ACCEPT_PX_BELOW, ORC_SB_TH_ACCEPT_PX_ABOVE, ORC_SB_TH_ACCEPT_PX_EQUAL,
+    ORC_SB_TH_OPP_GRAFT_BELOW, ORC_SB_TH_OPP_GRAFT_ABOVE, ORC_SB_TH_OPP_GRAFT_EQUAL,
+    /* score.go:276-279, 882-897: a record of a topic without score parameters skipped by score() */
+    ORC_SB_UNSCORED_SKIPPED,
+    ORC_SB_COUNT
+};
+void orc_score_census_enable(int on);
+void orc_score_census_reset(void);
+void orc_score_census_read(uint64_t* out);     /* [ORC_SB_COUNT] */
+
 /* The selection keys, for tests that restate a selection as "sort by key":
  * the key of item `col` at row position `pos` in the shuffle `purpose` of
  * (tick, observer, topic), and makePrune's key of a PX candidate (the purpose

@@ -159,7 +159,8 @@ static int cmp_arr(const void* a, const void* b)
 
 int64_t orc_layout_size(int32_t which)
 {
-    return which == 0 ? (int64_t)sizeof(orc_net) : which == 1 ? (int64_t)sizeof(orc_msgs) : -1;
+    return which == 0 ? (int64_t)sizeof(orc_net) : which == 1 ? (int64_t)sizeof(orc_msgs)
+           : which == 2 ? (int64_t)ORC_SB_COUNT : -1;      /* 2: the length of the score census table */
 }
 
 int64_t orc_round_time(const orc_msgs* m, int64_t g)
@@ -269,6 +270,7 @@ static void handle_copy(orc_net* s, orc_msgs* m, priv* p, int64_t g, int64_t now
 {
     const uint32_t i = x.recv, slot = x.slot, er = x.er;
     const int32_t t = (int32_t)m->topic[slot];
+    if (!(s->direct && s->direct[er])) orc_sb_cmp(ORC_SB_TH_GRAYLIST_BELOW, s->score[er], gray);
     if (s->score[er] < gray && !(s->direct && s->direct[er])) {   /* AcceptFrom -> AcceptNone; direct: AcceptAll */
         stats[3]++;
         return;
@@ -378,6 +380,8 @@ void orc_round(orc_net* s, orc_msgs* m, int64_t g)
             /* direct peers in the topic always get it (gossipsub.go:991-1003) */
             const int direct = s->direct && s->direct[e] && ((s->sub[i] >> t) & 1u);
             if (flood) {
+                if (!direct && ((s->sub[i] >> t) & 1u))
+                    orc_sb_cmp(ORC_SB_TH_PUBLISH_BELOW, s->score[e], s->th->publish_threshold);
                 if (!direct && (!((s->sub[i] >> t) & 1u) || s->score[e] < s->th->publish_threshold)) continue;
             } else if (!direct && !(s->tflags[(int64_t)t * s->e + e] & want)) {
                 continue;

@@ -130,6 +130,7 @@ void orc_gossip_emit(orc_net* s, orc_msgs* m, uint32_t i, int32_t t, uint64_t ti
         if (!topic_peer(s, e, t)) continue;
         if (s->tflags[te(s, t, e)] & exclude) continue;                    /* exclude: mesh / fanout */
         if (s->direct && s->direct[e]) continue;                           /* no gossip to direct peers */
+        if (orc_sb_on) orc_sb_cmp(ORC_SB_TH_GOSSIP_BELOW, orc_score_edge(s, e), s->th->gossip_threshold);
         if (orc_score_edge(s, e) < s->th->gossip_threshold) continue;        /* live Score(p) */
         L[n].key = okey(seed, tick, i, t, P_GOSSIP, s->col[e], e - b);
         L[n].v = e;
@@ -310,6 +311,7 @@ void orc_gossip_ihave(orc_net* s, orc_msgs* m, int64_t g)
             for (int32_t t = 0; t < s->t; ++t) any |= p->ihave[te(s, t, e)];
             if (!any) continue;
             const uint32_t i = s->col[e];
+            orc_sb_cmp(ORC_SB_TH_GOSSIP_BELOW, s->score[e], s->th->gossip_threshold);
             if (s->score[e] < s->th->gossip_threshold) continue;     /* IHAVE from a low-score peer */
             if (1 > gp->max_ihave_messages) continue;                 /* peerhave flood protection */
             if (0 >= gp->max_ihave_length) continue;                  /* iasked */
@@ -385,6 +387,7 @@ void orc_gossip_iwant(orc_net* s, orc_msgs* m, int64_t g)
     for (int64_t q = 0; q < p->niw; ++q) {
         const uint32_t er = p->iw[q].er, slot = p->iw[q].slot;   /* er: requester p's edge to i */
         const uint32_t i = s->col[er], ei = s->rev[er];          /* ei: i's edge to p */
+        orc_sb_cmp(ORC_SB_TH_GOSSIP_BELOW, s->score[ei], s->th->gossip_threshold);
         if (s->score[ei] < s->th->gossip_threshold) continue;     /* IWANT from a low-score peer */
         if (m->behaviour && (m->behaviour[i] & ORC_BEHAVE_IGNORE_IWANT)) continue;
         int64_t pt;

@@ -127,6 +127,29 @@ static inline void orc_census(int branch, uint32_t deg)
     orc_census_tab[branch][orc_row_class(deg)] += 1;
 }
 
+/* ---- score-branch census (oracle.h: orc_score_census_*) ------------------- */
+extern int32_t orc_sb_on;
+extern uint64_t orc_sb_tab[ORC_SB_COUNT];
+
+static inline void orc_sb(int ev)
+{
+    if (!orc_sb_on) return;
+#pragma omp atomic
+    orc_sb_tab[ev] += 1;
+}
+
+/* a comparison against one of the five thresholds: base + 0 below, + 1 above, + 2 equal */
+static inline void orc_sb_cmp(int base, double score, double thr)
+{
+    if (!orc_sb_on) return;
+    orc_sb(base + (score < thr ? 0 : score > thr ? 1 : 2));
+}
+
+/* the mesh credits one record took within the tick (oracle.c) */
+void orc_sb_pending_reset(const orc_net* s);
+void orc_sb_pending_inc(const orc_net* s, int64_t i);
+uint32_t orc_sb_pending(const orc_net* s, int64_t i);
+
 priv* orc_msgs_priv(orc_msgs* m);
 int64_t orc_round_time(const orc_msgs* m, int64_t g);
 

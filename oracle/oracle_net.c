@@ -138,6 +138,7 @@ static int px_list(hb* h, uint32_t ep, int live, uint32_t purpose, uint64_t key_
 /* the pruned peer's handlePrune PX part: acceptPXThreshold, then pxConnect */
 static void px_accept(orc_net* s, uint32_t ep, const uint32_t* listed, int n)
 {
+    orc_sb_cmp(ORC_SB_TH_ACCEPT_PX_BELOW, s->score[s->rev[ep]], s->th->accept_px_threshold);
     if (s->score[s->rev[ep]] < s->th->accept_px_threshold) return;
     const uint32_t p = s->col[ep];
     for (int q = 0; q < n; ++q) {
@@ -340,6 +341,7 @@ static void maintain(hb* h)
         qsort(sc, (size_t)n, sizeof(double), cmp_score_asc);
         double median = sc[n / 2];
         free(sc);
+        orc_sb_cmp(ORC_SB_TH_OPP_GRAFT_BELOW, median, s->th->opportunistic_graft_threshold);
         if (median < s->th->opportunistic_graft_threshold) {
             int total;
             int m = get_peers(h, gp->opportunistic_graft_peers, f_opp, median, P_GRAFT_OPP, c, &total);
@@ -386,6 +388,7 @@ static void fanout(hb* h, orc_msgs* m)
         int have = 0;
         for (uint32_t e = h->b; e < h->en; ++e) {
             if (!in_fanout(h, e)) continue;
+            if (topic_peer(h, e)) orc_sb_cmp(ORC_SB_TH_PUBLISH_BELOW, s->score[e], thr);
             if (!topic_peer(h, e) || s->score[e] < thr) s->tflags[ti(h, e)] &= (uint8_t)~GSIM_TF_FANOUT;
             else ++have;
         }

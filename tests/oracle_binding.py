@@ -143,6 +143,9 @@ def load():
             "orc_census_enable": (None, [ctypes.c_int]),
             "orc_census_reset": (None, []),
             "orc_census_read": (None, [c_void_p]),
+            "orc_score_census_enable": (None, [ctypes.c_int]),
+            "orc_score_census_reset": (None, []),
+            "orc_score_census_read": (None, [c_void_p]),
             "orc_select_key": (c_uint64, [c_uint64, c_uint64, c_uint32, c_int32, c_uint32, c_uint32, c_uint32]),
             "orc_px_key": (c_uint64, [c_uint64, c_uint64, c_uint32, c_int32, c_uint32, c_uint32, c_uint32, c_uint32]),
         }
@@ -347,6 +350,47 @@ class Census:
     def __exit__(self, *exc):
         self.read()
         load().orc_census_enable(0)
+        return False
+
+
+# oracle.h ORC_SB_*: the score-branch census, one count per event (mesh_pending_max: a maximum)
+SCORE_CENSUS = (
+    "p1_uncapped", "p1_capped", "p1_at_cap", "p1_negative", "act_set", "act_edge",
+    "p3_deficit", "p3_at_threshold", "p3_inactive", "prune_deficit", "prune_no_deficit", "prune_pending",
+    "first_below", "first_reach", "first_at", "mesh_below", "mesh_reach", "mesh_at", "mesh_pending_max",
+    "decay_first_zero", "decay_first_edge", "decay_meshd_zero", "decay_meshd_edge", "decay_fail_zero",
+    "decay_fail_edge", "decay_invalid_zero", "decay_invalid_edge", "decay_bp_zero", "decay_bp_edge",
+    "tsc_applied", "tsc_at_cap", "tsc_negative", "p6_surplus", "p6_at_threshold", "p6_whitelisted", "p6_multi_ip",
+    "p7_excess", "p7_at_threshold", "retain_purged", "retain_edge", "retain_skipped",
+    "win_inside", "win_outside", "win_edge",
+    "th_gossip_below", "th_gossip_above", "th_gossip_equal", "th_publish_below", "th_publish_above",
+    "th_publish_equal", "th_graylist_below", "th_graylist_above", "th_graylist_equal",
+    "th_accept_px_below", "th_accept_px_above", "th_accept_px_equal",
+    "th_opp_graft_below", "th_opp_graft_above", "th_opp_graft_equal", "unscored_skipped")
+
+
+class ScoreCensus:
+    """Counts the oracle's scoring, credit and threshold events while open;
+    .table maps an event name to its count."""
+
+    def __enter__(self):
+        lib = load()
+        lib.orc_score_census_reset()
+        lib.orc_score_census_enable(1)
+        self.table = None
+        return self
+
+    def read(self):
+        assert load().orc_layout_size(2) == len(SCORE_CENSUS), "SCORE_CENSUS and oracle.h ORC_SB_* differ in length"
+        out = np.zeros(len(SCORE_CENSUS), dtype=np.uint64)
+        load().orc_score_census_read(out.ctypes.data_as(c_void_p))
+        self.table = {b: int(out[q]) for q, b in enumerate(SCORE_CENSUS)}
+        return self.table
+
+    def __exit__(self, *exc):
+        self.read()
+        lib = load()
+        lib.orc_score_census_enable(0)
         return False
 
 

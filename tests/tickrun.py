@@ -172,7 +172,7 @@ def run_parity(net, params, th, gp, st, ticks, sched, ring=256, behaviour=None, 
             lput = eng.read(_abi.F_LASTPUT, into=msgs.lastput.copy()) if local_only else eng.read(_abi.F_LASTPUT)
             assert np.array_equal(seen, msgs.seen), f"seen-set differs at tick {kk}"
             assert np.array_equal(lput, msgs.lastput), f"mcache puts differ at tick {kk}"
-            gpu = ob.NetState(net, params, thresholds=th, gossip=gp)
+            gpu = ob.NetState(net, params, thresholds=th, gossip=gp, topics=st.topics)   # (unscored topics too)
             gpu.pull_from_engine(eng, base=st if local_only else None)
             assert_same(st, gpu)
             if trace is not None:
