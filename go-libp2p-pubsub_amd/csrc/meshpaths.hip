@@ -64,7 +64,7 @@
 #include <cstring>
 #include <vector>
 
-#include "gsim_internal.h"
+#include "report_common.h"
 
 namespace gsim {
 
@@ -174,13 +174,6 @@ __global__ __launch_bounds__(GSIM_PATH_SOURCES) void k_mp_seed(PathArgs a, PathS
     else atomicOr((unsigned long long*)&a.cur[s], bit);
 }
 
-__device__ __forceinline__ uint64_t wave_or(uint64_t v)
-{
-#pragma unroll
-    for (int o = 32; o; o >>= 1) v |= (uint64_t)__shfl_xor((unsigned long long)v, o, 64);
-    return v;
-}
-
 template <bool CLS, bool L0>
 __global__ __launch_bounds__(kPathBlock) void k_mp_fold(PathArgs a)
 {
@@ -272,25 +265,13 @@ __global__ __launch_bounds__(kPathBlock) void k_mp_fold(PathArgs a)
 template <bool Dense>
 void launch_push(gsim_handle* h, const PathArgs& a)
 {
-    RowClasses rc{};
-    row_classes(h, &rc);
-    auto grid = [](int64_t groups, int per_block) {
-        return dim3((uint32_t)std::max<int64_t>(1, std::min<int64_t>((groups + per_block - 1) / per_block, 2048)));
-    };
-    const uint32_t* r = rc.rows;
-    const int64_t b0 = r ? 0 : h->olo();
-    // (without lists one class holds every owned row, in order from olo)
-    if (rc.n16)
-        hipLaunchKernelGGL((k_mp_push<16, Dense>), grid(rc.n16, 16), dim3(kPathBlock), 0, h->stream, a, r, rc.n16, b0);
-    if (rc.n32)
-        hipLaunchKernelGGL((k_mp_push<32, Dense>), grid(rc.n32, 8), dim3(kPathBlock), 0, h->stream, a,
-                           r ? r + rc.n16 : r, rc.n32, b0);
-    if (rc.n64)
-        hipLaunchKernelGGL((k_mp_push<64, Dense>), grid(rc.n64, 4), dim3(kPathBlock), 0, h->stream, a,
-                           r ? r + rc.n16 + rc.n32 : r, rc.n64, b0);
-    if (rc.nhub && r)
-        hipLaunchKernelGGL((k_mp_push_hub<Dense>), dim3((uint32_t)std::min<int64_t>(rc.nhub, 1024)), dim3(kPathBlock), 0,
-                           h->stream, a, r + rc.n16 + rc.n32 + rc.n64, rc.nhub);
+    launch_row_classes(h, kPathBlock, [&](auto w, dim3 grid, const uint32_t* rows, int64_t nrows, int64_t base) {
+        constexpr int W = decltype(w)::value;
+        if constexpr (W == 0)
+            hipLaunchKernelGGL((k_mp_push_hub<Dense>), grid, dim3(kPathBlock), 0, h->stream, a, rows, nrows);
+        else
+            hipLaunchKernelGGL((k_mp_push<W, Dense>), grid, dim3(kPathBlock), 0, h->stream, a, rows, nrows, base);
+    });
 }
 
 PathArgs path_args(gsim_handle* h)
@@ -320,11 +301,7 @@ void meshpaths_release(gsim_handle* h)
 {
     if (!h->mp) return;
     MeshPaths* r = h->mp;
-    if (r->d_words) (void)hipFree(r->d_words);
-    if (r->d_inc) (void)hipFree(r->d_inc);
-    if (r->d_acc) (void)hipFree(r->d_acc);
-    if (r->d_any) (void)hipFree(r->d_any);
-    if (r->d_pp) (void)hipFree(r->d_pp);
+    free_all({r->d_words, r->d_inc, r->d_acc, r->d_any, r->d_pp});
     delete r;
     h->mp = nullptr;
 }
@@ -336,15 +313,14 @@ int meshpaths_begin(gsim_handle* h, int32_t topic, const uint32_t* src_local, in
     if (!h->mp) h->mp = new MeshPaths;
     MeshPaths* r = h->mp;
     const size_t n = (size_t)std::max<int64_t>(h->n, 1), own = (size_t)std::max<int64_t>(h->ohi() - h->olo(), 1);
-    hipError_t e = hipSuccess;
-    if (!r->d_words) e = hipMalloc((void**)&r->d_words, sizeof(uint64_t) * 3 * n);
-    if (e == hipSuccess && !r->d_acc) e = hipMalloc((void**)&r->d_acc, sizeof(uint32_t) * kPathAcc);
-    if (e == hipSuccess && !r->d_any) e = hipMalloc((void**)&r->d_any, sizeof(unsigned long long) * 2);
-    if (e == hipSuccess && h->sh && !r->d_inc) e = hipMalloc((void**)&r->d_inc, sizeof(uint64_t) * own);
-    if (e == hipSuccess && per_peer && !r->d_pp) e = hipMalloc((void**)&r->d_pp, sizeof(uint32_t) * 2 * n);
-    if (e != hipSuccess) { h->err = std::string("report scratch: ") + hipGetErrorString(e); return GSIM_ENOMEM; }
+    int rc = alloc_once(h, "report", &r->d_words, (int64_t)(3 * n));
+    if (!rc) rc = alloc_once(h, "report", &r->d_acc, kPathAcc);
+    if (!rc) rc = alloc_once(h, "report", &r->d_any, 2);
+    if (!rc && h->sh) rc = alloc_once(h, "report", &r->d_inc, (int64_t)own);
+    if (!rc && per_peer) rc = alloc_once(h, "report", &r->d_pp, (int64_t)(2 * n));
+    if (rc) return rc;
     r->topic = topic; r->nsrc = n_sources; r->blocked = blocked; r->per_peer = per_peer;
-    e = hipMemsetAsync(r->d_words, 0, sizeof(uint64_t) * 3 * n, h->stream);
+    hipError_t e = hipMemsetAsync(r->d_words, 0, sizeof(uint64_t) * 3 * n, h->stream);
     if (e == hipSuccess) e = hipMemsetAsync(r->d_acc, 0, sizeof(uint32_t) * kPathAcc, h->stream);
     if (e == hipSuccess) e = hipMemsetAsync(r->d_any, 0, sizeof(unsigned long long) * 2, h->stream);
     if (e == hipSuccess && per_peer) e = hipMemsetAsync(r->d_pp, 0, sizeof(uint32_t) * 2 * n, h->stream);

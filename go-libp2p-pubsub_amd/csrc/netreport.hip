@@ -54,7 +54,7 @@
 #include <limits>
 #include <vector>
 
-#include "gsim_internal.h"
+#include "report_common.h"
 
 namespace gsim {
 
@@ -99,11 +99,6 @@ struct NetArgs {
     int32_t sharded;
     uint32_t olo, ohi;
     unsigned long long* acc;                   // this pass's counters
-};
-
-struct NetEdges {
-    double v[GSIM_NET_SCORE_BINS - 1];
-    int32_t n;
 };
 
 namespace {
@@ -277,7 +272,7 @@ __global__ __launch_bounds__(kNetBlock) void k_net_mesh_hub(NetArgs a, const uin
 
 // (min / max: f64_key / key_f64, gsim_internal.h)
 template <bool CLS>
-__global__ __launch_bounds__(kNetBlock) void k_net_score(NetArgs a, NetEdges ed)
+__global__ __launch_bounds__(kNetBlock) void k_net_score(NetArgs a, ScoreEdges ed)
 {
     __shared__ uint32_t s_cnt[kMaxPairs * kSFCount];
     __shared__ unsigned long long s_mm[kMaxPairs * 2];            // per pair: max of ~key, max of key
@@ -305,14 +300,7 @@ __global__ __launch_bounds__(kNetBlock) void k_net_score(NetArgs a, NetEdges ed)
 #pragma unroll
         for (int k = 0; k < GSIM_NET_SCORE_BINS - 1; ++k) bin += (k < ed.n && s >= ed.v[k]) ? 1u : 0u;
         const uint32_t key = pair * kSFCount + (conn ? (isn ? (uint32_t)SF_NAN : bin) : (uint32_t)SF_RET);
-        uint64_t todo = __ballot(act);
-        while (todo) {                                            // wave-uniform: the distinct keys present
-            const int lead = __builtin_ctzll(todo);
-            const uint32_t k = (uint32_t)__builtin_amdgcn_readlane((int)key, lead);
-            const uint64_t same = __ballot(act && key == k);
-            if ((int)(threadIdx.x & 63) == lead) atomicAdd(&s_cnt[k], (uint32_t)__popcll(same));
-            todo &= ~same;
-        }
+        count_keys(s_cnt, act, key, (int)(threadIdx.x & 63));      // the distinct keys present
         if (conn && !isn) {
             const unsigned long long kk = f64_key(s);
             volatile unsigned long long* mm = s_mm + pair * 2;
@@ -336,25 +324,13 @@ template <bool Dense, bool CLS>
 void launch_mesh(gsim_handle* h, const NetArgs& a)
 {
     const size_t lds = sizeof(uint32_t) * (size_t)a.T * (size_t)a.C * kMF;
-    RowClasses rc{};
-    row_classes(h, &rc);
-    auto grid = [](int64_t groups, int per_block) {
-        return dim3((uint32_t)std::max<int64_t>(1, std::min<int64_t>((groups + per_block - 1) / per_block, 2048)));
-    };
-    const uint32_t* r = rc.rows;
-    const int64_t b0 = r ? 0 : h->olo();
-    // (without lists one class holds every owned row, in order from olo)
-    if (rc.n16)
-        hipLaunchKernelGGL((k_net_mesh<16, Dense, CLS>), grid(rc.n16, 16), dim3(kNetBlock), lds, h->stream, a, r, rc.n16, b0);
-    if (rc.n32)
-        hipLaunchKernelGGL((k_net_mesh<32, Dense, CLS>), grid(rc.n32, 8), dim3(kNetBlock), lds, h->stream, a,
-                           r ? r + rc.n16 : r, rc.n32, b0);
-    if (rc.n64)
-        hipLaunchKernelGGL((k_net_mesh<64, Dense, CLS>), grid(rc.n64, 4), dim3(kNetBlock), lds, h->stream, a,
-                           r ? r + rc.n16 + rc.n32 : r, rc.n64, b0);
-    if (rc.nhub && r)
-        hipLaunchKernelGGL((k_net_mesh_hub<Dense, CLS>), dim3((uint32_t)std::min<int64_t>(rc.nhub, 1024)), dim3(kNetBlock),
-                           lds, h->stream, a, r + rc.n16 + rc.n32 + rc.n64, rc.nhub);
+    launch_row_classes(h, kNetBlock, [&](auto w, dim3 grid, const uint32_t* rows, int64_t nrows, int64_t base) {
+        constexpr int W = decltype(w)::value;
+        if constexpr (W == 0)
+            hipLaunchKernelGGL((k_net_mesh_hub<Dense, CLS>), grid, dim3(kNetBlock), lds, h->stream, a, rows, nrows);
+        else
+            hipLaunchKernelGGL((k_net_mesh<W, Dense, CLS>), grid, dim3(kNetBlock), lds, h->stream, a, rows, nrows, base);
+    });
 }
 
 }  // namespace
@@ -365,8 +341,7 @@ using namespace gsim;
 void netreport_release(gsim_handle* h)
 {
     if (!h->nr) return;
-    if (h->nr->d_cls) (void)hipFree(h->nr->d_cls);
-    if (h->nr->d_acc) (void)hipFree(h->nr->d_acc);
+    free_all({h->nr->d_cls, h->nr->d_acc});
     delete h->nr;
     h->nr = nullptr;
 }
@@ -423,19 +398,8 @@ int gsim_net_report(gsim_handle* h, const double* edges, int32_t n_edges, struct
     *n_scores = ns;
     if (hipSetDevice(h->device) != hipSuccess) return GSIM_EDEVICE;
     if (h->e == 0 && h->n == 0) { h->err = "no graph loaded (call gsim_load_graph first)"; return GSIM_ESTATE; }
-    if (n_edges < 0 || n_edges > GSIM_NET_SCORE_BINS - 1 || (n_edges > 0 && !edges)) {
-        h->err = "gsim_net_report: n_edges must lie in 0..15";
-        return GSIM_EINVAL;
-    }
-    NetEdges ed{};
-    ed.n = n_edges;
-    for (int k = 0; k < n_edges; ++k) {
-        if (edges[k] != edges[k] || (k > 0 && !(edges[k] > edges[k - 1]))) {
-            h->err = "gsim_net_report: the edges must be strictly ascending, without NaN";
-            return GSIM_EINVAL;
-        }
-        ed.v[k] = edges[k];
-    }
+    ScoreEdges ed{};
+    if (int rc = score_edges(h, "gsim_net_report", edges, n_edges, &ed)) return rc;
     const bool want_mesh = mesh && mesh_cap > 0, want_scores = scores && score_cap > 0;
     if ((want_mesh && mesh_cap < nm) || (want_scores && score_cap < ns)) {
         h->err = "gsim_net_report: output buffer too small";
@@ -444,11 +408,9 @@ int gsim_net_report(gsim_handle* h, const double* edges, int32_t n_edges, struct
     if (!want_mesh && !want_scores) return GSIM_OK;
     if (!h->nr) h->nr = new NetReport;
     NetReport* r = h->nr;
-    hipError_t e = hipSuccess;
-    if (!r->d_acc) e = hipMalloc((void**)&r->d_acc, sizeof(unsigned long long) * kAccWords);
-    if (e != hipSuccess) { h->err = std::string("report scratch: ") + hipGetErrorString(e); return GSIM_ENOMEM; }
+    if (int rc = alloc_once(h, "report", &r->d_acc, (int64_t)kAccWords)) return rc;
     const size_t mesh_words = (size_t)nm * kMF, score_words = (size_t)ns * kSF;
-    e = hipMemsetAsync(r->d_acc, 0, sizeof(unsigned long long) * kAccWords, h->stream);
+    hipError_t e = hipMemsetAsync(r->d_acc, 0, sizeof(unsigned long long) * kAccWords, h->stream);
     if (e != hipSuccess) return hip_check(h, e, "gsim_net_report");
 
     NetArgs a{};

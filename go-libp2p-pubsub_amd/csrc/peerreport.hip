@@ -8,10 +8,11 @@
 // first (markFirstMessageDelivery's peer, score.go:919-946).
 //
 // Launches per call (none per slot or per peer, no host loop over either):
-//   k_peer_select   one block: the slots published in [round_lo, round_hi),
-//                   report.hip's selection, compacted in slot order with what the
-//                   walk needs of each (cell base and count, publication round,
-//                   topic, origin), and the selected messages per topic
+//   k_select<PrFill>  one block: the slots published in [round_lo, round_hi),
+//                   the reports' shared selection (report_common.h), compacted in
+//                   slot order with what the walk needs of each (cell base and
+//                   count, publication round, topic, origin), and the selected
+//                   messages per topic
 //   k_peer_reduce   a lane owns a peer, a wave the 64 peers of one word of the
 //                   member bitmaps, and walks the selected slots: 512 contiguous
 //                   bytes per slot on the dense ring; on a member-compacted topic
@@ -48,7 +49,7 @@
 //   k_peer_reduce<false>  38 VGPRs, 94 SGPRs, no spills, 8 waves/SIMD
 //   k_peer_reduce<true>   49 VGPRs, 106 SGPRs, 36 of them kept in lanes of one VGPR
 //                         (kernel arguments), no VGPR spills, 7 waves/SIMD
-//   k_peer_select         28 VGPRs, 53 SGPRs, 324 bytes of LDS, 8 waves/SIMD
+//   k_select<PrFill>      28 VGPRs, 53 SGPRs, 324 bytes of LDS, 8 waves/SIMD
 // Measured: C3 after the default bench's ticks, 1477 messages,
 // 11.8 GB of cells: the per-peer rows alone 3.13 ms, both halves 6.56 ms with one
 // class and 14.0 ms with two, against 2.20 ms for gsim_msg_report on the same
@@ -58,17 +59,11 @@
 #include <cstring>
 #include <vector>
 
-#include "gsim_internal.h"
+#include "report_common.h"
 
 namespace gsim {
 
-// one selected message as the walk reads it
-struct PrMsg {
-    uint64_t base;      // first cell of the slot
-    uint32_t len;       // its cells (peers, or members of its topic)
-    uint32_t pub;       // publication round
-    uint32_t topic, origin;
-};
+using PrMsg = SelMsg;   // one selected message as the walk reads it (report_common.h)
 
 // per (topic, class) counters: u32 words in LDS, u64 in global memory, the same index
 enum : int {
@@ -91,7 +86,7 @@ struct PeerReport {
     unsigned long long* d_acc = nullptr;       // [kPrAcc]
     gsim_peer_row* d_rows = nullptr;           // [rows_cap]
     int64_t rows_cap = 0;
-    int32_t ring = 0;
+    int64_t ring = 0;
     int64_t last[3] = {0, 0, 0};               // gsim_peer_report_launch
 };
 
@@ -115,60 +110,22 @@ namespace {
 
 constexpr int kPrBlock = 256;                  // 4 waves, 256 consecutive peers
 constexpr int kPrBatch = 4;                    // slots whose cells a lane has in flight
-constexpr int kPrSelBlock = 1024;
 constexpr int64_t kPrFullWaves = 256;          // one wave per CU: from here on peers alone fill the device
 constexpr int64_t kPrTargetWaves = 2048;       // what a split grid aims at
 constexpr int64_t kPrMinSlots = 2 * kPrBatch;  // a part walks at least two batches
 
-// report.hip's k_report_select with the walk's row in place of the report's.
-__global__ __launch_bounds__(kPrSelBlock) void k_peer_select(ReportView v, int64_t lo, int64_t hi, PrMsg* sel, uint32_t* cnt)
-{
-    __shared__ uint32_t s_w[kPrSelBlock / 64];
-    __shared__ uint32_t s_base;
-    __shared__ uint32_t s_nm[GSIM_MAX_TOPICS];
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    if (tid == 0) s_base = 0;
-    if (tid < GSIM_MAX_TOPICS) s_nm[tid] = 0;
-    __syncthreads();
-    for (int m0 = 0; m0 < v.ring; m0 += kPrSelBlock) {
-        const int m = m0 + tid;
-        bool pick = false;
-        int64_t pub = 0;
-        if (m < v.ring && v.slot_last[m] >= 0) {               // published at least once
-            pub = v.mpub[m];
-            pick = pub >= lo && pub < hi;
-        }
-        const uint64_t b = __ballot(pick);
-        if (lane == 0) s_w[w] = (uint32_t)__popcll(b);
-        __syncthreads();
-        uint32_t pos = s_base + (uint32_t)__popcll(b & ((1ull << lane) - 1ull));
-        for (int q = 0; q < w; ++q) pos += s_w[q];
-        if (pick) {
-            const int64_t base = (int64_t)v.cells.cbase[m];
-            const int64_t end = (int64_t)m + 1 < v.ring ? (int64_t)v.cells.cbase[m + 1] : v.ncells;
-            PrMsg x;
-            x.base = (uint64_t)base;
-            x.len = (uint32_t)(end > base ? end - base : 0);
-            x.pub = (uint32_t)pub;
-            x.topic = v.mtopic[m];
-            x.origin = v.morigin[m];
-            sel[pos] = x;
-            if (x.topic < (uint32_t)GSIM_MAX_TOPICS) atomicAdd(&s_nm[x.topic], 1u);
-        }
-        __syncthreads();
-        if (tid == 0) {
-            uint32_t tot = 0;
-            for (int q = 0; q < kPrSelBlock / 64; ++q) tot += s_w[q];
-            s_base += tot;
-        }
-        __syncthreads();
+// The selected slot's row (k_select, report_common.h).
+struct PrFill {
+    using Row = PrMsg;
+    __device__ static uint32_t fill(Row& r, const ReportView& v, int m, int64_t pub)
+    {
+        PrMsg x;
+        fill_sel(x, v, m, pub);
+        r = x;
+        return x.topic;
     }
-    if (tid == 0) {
-        cnt[PC_NSEL] = s_base;
-        cnt[PC_BAD] = 0;
-    }
-    if (tid < GSIM_MAX_TOPICS) cnt[PC_TOPIC + tid] = s_nm[tid];
-}
+};
+static_assert(PC_NSEL == 0 && PC_BAD < PC_TOPIC, "k_select<PrFill, PC_TOPIC> writes the count and clears the flag");
 
 template <bool CLS>
 __global__ __launch_bounds__(kPrBlock) void k_peer_reduce(PeerArgs a)
@@ -186,18 +143,12 @@ __global__ __launch_bounds__(kPrBlock) void k_peer_reduce(PeerArgs a)
     const bool wave_on = word * 64 < a.qhi;                    // (the grid's last block may hold idle waves)
     const uint64_t sub = active ? a.sub[p] : 0ull;
     const uint32_t mycls = CLS && active ? a.cls[p] : 0u;
-    const uint64_t below = (1ull << lane) - 1ull;
 
     if (classes && blockIdx.y == 0) {                          // peers of each class announcing each topic
         for (int32_t t = 0; t < a.T; ++t) {
-            uint64_t todo = __ballot((sub >> t) & 1ull);
-            while (todo) {                                     // wave-uniform: the classes present
-                const int lead = __builtin_ctzll(todo);
-                const uint32_t cl = CLS ? (uint32_t)__builtin_amdgcn_readlane((int)mycls, lead) : 0u;
-                const uint64_t same = __ballot(((sub >> t) & 1ull) && mycls == cl);
-                if (lane == lead) atomicAdd(&s_acc[(t * a.C + (int)cl) * kPL + PL_PEERS], (uint32_t)__popcll(same));
-                todo &= ~same;
-            }
+            // the classes present
+            lead_keys((sub >> t) & 1ull, mycls, lane,
+                      [&](uint32_t cl, uint32_t cnt) { atomicAdd(&s_acc[(t * a.C + (int)cl) * kPL + PL_PEERS], cnt); });
         }
     }
 
@@ -227,8 +178,7 @@ __global__ __launch_bounds__(kPrBlock) void k_peer_reduce(PeerArgs a)
                     wpre = 0;
                     if (wave_on) a.cells.word(t, word, wbits, wpre);
                 }
-                has = (wbits >> lane) & 1ull;
-                idx = wpre + __popcll(wbits & below);
+                member_rank(wbits, wpre, lane, has, idx);
             }
             c[u] = kUnseen64;
             if (on && active && has && idx < (int64_t)mm[u].len) c[u] = a.cells.cell[(int64_t)mm[u].base + idx];
@@ -267,6 +217,8 @@ __global__ __launch_bounds__(kPrBlock) void k_peer_reduce(PeerArgs a)
             ff3 += other && sc[u] == 3;
             if (!classes || t >= a.T) continue;
             uint32_t* trow = s_acc + t * a.C * kPL;            // the topic's rows, one per class
+            // (the three walks below stay written out: through lead_keys the one-class kernel
+            // measured 2.8 % slower than before, outside the spread of repeated runs)
             uint64_t todo = __ballot(ok);
             while (todo) {                                     // wave-uniform: the distinct (class, latency) present
                 const int lead = __builtin_ctzll(todo);
@@ -369,10 +321,7 @@ void peerreport_release(gsim_handle* h)
 {
     if (!h->pr) return;
     PeerReport* r = h->pr;
-    if (r->d_sel) (void)hipFree(r->d_sel);
-    if (r->d_cnt) (void)hipFree(r->d_cnt);
-    if (r->d_acc) (void)hipFree(r->d_acc);
-    if (r->d_rows) (void)hipFree(r->d_rows);
+    free_all({r->d_sel, r->d_cnt, r->d_acc, r->d_rows});
     delete r;
     h->pr = nullptr;
 }
@@ -381,30 +330,11 @@ static int peerreport_scratch(gsim_handle* h, int32_t ring, int64_t rows)
 {
     if (!h->pr) h->pr = new PeerReport;
     PeerReport* r = h->pr;
-    hipError_t e = hipSuccess;
-    if (r->ring < ring) {
-        (void)hipStreamSynchronize(h->stream);
-        if (r->d_sel) (void)hipFree(r->d_sel);
-        r->d_sel = nullptr;
-        r->ring = 0;
-        e = hipMalloc((void**)&r->d_sel, sizeof(PrMsg) * (size_t)std::max<int32_t>(ring, 1));
-        if (e == hipSuccess) r->ring = ring;
-    }
-    if (e == hipSuccess && !r->d_cnt) e = hipMalloc((void**)&r->d_cnt, sizeof(uint32_t) * kPC);
-    if (e == hipSuccess && !r->d_acc) e = hipMalloc((void**)&r->d_acc, sizeof(unsigned long long) * kPrAcc);
-    if (e == hipSuccess && r->rows_cap < rows) {
-        (void)hipStreamSynchronize(h->stream);
-        if (r->d_rows) (void)hipFree(r->d_rows);
-        r->d_rows = nullptr;
-        r->rows_cap = 0;
-        e = hipMalloc((void**)&r->d_rows, sizeof(gsim_peer_row) * (size_t)rows);
-        if (e == hipSuccess) r->rows_cap = rows;
-    }
-    if (e != hipSuccess) {
-        h->err = std::string("peer report scratch: ") + hipGetErrorString(e);
-        return GSIM_ENOMEM;
-    }
-    return GSIM_OK;
+    int rc = grow(h, "peer report", &r->d_sel, &r->ring, std::max<int64_t>(ring, 1));
+    if (!rc) rc = alloc_once(h, "peer report", &r->d_cnt, kPC);
+    if (!rc) rc = alloc_once(h, "peer report", &r->d_acc, (int64_t)kPrAcc);
+    if (!rc) rc = grow(h, "peer report", &r->d_rows, &r->rows_cap, rows);
+    return rc;
 }
 
 extern "C" {
@@ -436,7 +366,8 @@ int gsim_peer_report(gsim_handle* h, int64_t round_lo, int64_t round_hi, int64_t
     if (!rc) rc = peerreport_scratch(h, v.ring, want_peers ? ohi - olo : 0);
     if (rc) return rc;
     PeerReport* r = h->pr;
-    hipLaunchKernelGGL(k_peer_select, dim3(1), dim3(kPrSelBlock), 0, h->stream, v, round_lo, round_hi, r->d_sel, r->d_cnt);
+    hipLaunchKernelGGL((k_select<PrFill, PC_TOPIC>), dim3(1), dim3(kSelBlock), 0, h->stream, v, round_lo, round_hi, r->d_sel,
+                       r->d_cnt);
     uint32_t cs[kPC] = {};
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipMemcpyAsync(cs, r->d_cnt, sizeof(cs), hipMemcpyDeviceToHost, h->stream);

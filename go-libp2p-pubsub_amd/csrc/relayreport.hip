@@ -7,7 +7,7 @@
 // took.  The reference has no such read-out; what is counted is the peer that
 // markFirstMessageDelivery credits (score.go:919-946), summed at that peer.
 //
-// The selected slots (report.hip's selection, k_relay_select) are processed in
+// The selected slots (the reports' shared selection, k_select<RlFill>) are processed in
 // batches of B.  The batch's scratch is cnt[B][n] (u32 children) and dep[B][n]
 // (u16 depth code), indexed by the LOCAL PEER ID on the dense ring and on
 // member-compacted sub-rings alike: a first sender is a local id, so a parent's
@@ -68,8 +68,8 @@
 //   k_relay_fold<true>    30 VGPRs, 57 SGPRs, likewise
 //   k_relay_depth         12 VGPRs, 30 SGPRs, no LDS
 //   k_relay_bins           6 VGPRs, 20 SGPRs, 132 bytes of LDS
-//   k_relay_select        30 VGPRs, 53 SGPRs, 324 bytes of LDS
-//   k_relay_peers<CLS>   8-10 VGPRs, 22-25 SGPRs, no LDS;  k_relay_add 8 VGPRs, 20 SGPRs
+//   k_select<RlFill>      30 VGPRs, 53 SGPRs, 324 bytes of LDS
+//   k_relay_peers<CLS>   8-10 VGPRs, 22-26 SGPRs, no LDS;  k_relay_add 8 VGPRs, 20 SGPRs
 // Measured (profiles/relay_report_c3.txt): C3 after the default
 // bench's ticks, 1477 messages, 1.43e9 first deliveries, batches of 44 slots: the
 // per-peer rows 96.0 ms, with the class rows 101.0, with the message rows 187.5
@@ -81,11 +81,11 @@
 #include <cstring>
 #include <vector>
 
-#include "gsim_internal.h"
+#include "report_common.h"
 
 namespace gsim {
 
-// one selected message as the walk reads it
+// one selected message as the walk reads it: SelMsg's fields (report_common.h), then the slot
 struct RlMsg {
     uint64_t base;      // first cell of the slot
     uint32_t len;       // its cells
@@ -143,10 +143,10 @@ struct RelayArgs {
 
 struct RelayReport {
     RlMsg* d_sel = nullptr;
-    int32_t ring = 0;
     uint32_t* d_flags = nullptr;
     unsigned long long* d_acc = nullptr;
     uint32_t* d_macc = nullptr;                  // [ring][kRM]
+    int64_t sel_cap = 0, macc_cap = 0;           // entries of sel, words of macc
     uint32_t* d_cnt = nullptr;
     uint16_t* d_dep = nullptr;
     uint32_t* d_inc = nullptr;                   // a shard: the ghosts' counts from the other shards
@@ -168,88 +168,25 @@ struct RelayReport {
 
 namespace {
 
+constexpr char kRlName[] = "relay report";      // (the scratch error text)
 constexpr int kRlBlock = 256;                    // 4 waves, 256 consecutive peers
-constexpr int kRlSelBlock = 1024;
 constexpr int64_t kRlFullWaves = 256;
 constexpr int64_t kRlTargetWaves = 2048;
 
-// report.hip's k_report_select with the walk's row in place of the report's.
-__global__ __launch_bounds__(kRlSelBlock) void k_relay_select(ReportView v, int64_t lo, int64_t hi, RlMsg* sel, uint32_t* cnt)
-{
-    __shared__ uint32_t s_w[kRlSelBlock / 64];
-    __shared__ uint32_t s_base;
-    __shared__ uint32_t s_nm[GSIM_MAX_TOPICS];
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    if (tid == 0) s_base = 0;
-    if (tid < GSIM_MAX_TOPICS) s_nm[tid] = 0;
-    __syncthreads();
-    for (int m0 = 0; m0 < v.ring; m0 += kRlSelBlock) {
-        const int m = m0 + tid;
-        bool pick = false;
-        int64_t pub = 0;
-        if (m < v.ring && v.slot_last[m] >= 0) {               // published at least once
-            pub = v.mpub[m];
-            pick = pub >= lo && pub < hi;
-        }
-        const uint64_t b = __ballot(pick);
-        if (lane == 0) s_w[w] = (uint32_t)__popcll(b);
-        __syncthreads();
-        uint32_t pos = s_base + (uint32_t)__popcll(b & ((1ull << lane) - 1ull));
-        for (int q = 0; q < w; ++q) pos += s_w[q];
-        if (pick) {
-            const int64_t base = (int64_t)v.cells.cbase[m];
-            const int64_t end = (int64_t)m + 1 < v.ring ? (int64_t)v.cells.cbase[m + 1] : v.ncells;
-            RlMsg x;
-            x.base = (uint64_t)base;
-            x.len = (uint32_t)(end > base ? end - base : 0);
-            x.pub = (uint32_t)pub;
-            x.topic = v.mtopic[m];
-            x.origin = v.morigin[m];
-            x.slot = (uint32_t)m;
-            x._pad = 0;
-            sel[pos] = x;
-            if (x.topic < (uint32_t)GSIM_MAX_TOPICS) atomicAdd(&s_nm[x.topic], 1u);
-        }
-        __syncthreads();
-        if (tid == 0) {
-            uint32_t tot = 0;
-            for (int q = 0; q < kRlSelBlock / 64; ++q) tot += s_w[q];
-            s_base += tot;
-        }
-        __syncthreads();
+// The selected slot's row (k_select, report_common.h).
+struct RlFill {
+    using Row = RlMsg;
+    __device__ static uint32_t fill(Row& r, const ReportView& v, int m, int64_t pub)
+    {
+        RlMsg x;
+        fill_sel(x, v, m, pub);
+        x.slot = (uint32_t)m;
+        x._pad = 0;
+        r = x;
+        return x.topic;
     }
-    if (tid == 0) cnt[RF_NSEL] = s_base;
-    if (tid > 0 && tid < RF_TOPIC) cnt[tid] = 0;
-    if (tid < GSIM_MAX_TOPICS) cnt[RF_TOPIC + tid] = s_nm[tid];
-}
-
-// the lane's cell of slot mm (kUnseen64: it has none); word is wave-uniform
-__device__ __forceinline__ uint64_t lane_cell(const Cells& cells, const RlMsg& mm, int64_t word, int lane, bool wave_on,
-                                              bool active)
-{
-    const int32_t t = (int32_t)mm.topic;
-    bool has = true;
-    int64_t idx = word * 64 + lane;
-    if ((cells.sparse >> t) & 1ull) {                          // wave-uniform
-        uint64_t wbits = 0;
-        int64_t wpre = 0;
-        if (wave_on) cells.word(t, word, wbits, wpre);
-        has = (wbits >> lane) & 1ull;
-        idx = wpre + __popcll(wbits & ((1ull << lane) - 1ull));
-    }
-    if (active && has && idx < (int64_t)mm.len) return cells.cell[(int64_t)mm.base + idx];
-    return kUnseen64;
-}
-
-__device__ __forceinline__ uint32_t wave_max(uint32_t x)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const uint32_t y = (uint32_t)__shfl_xor((int)x, off, 64);
-        x = y > x ? y : x;
-    }
-    return x;
-}
+};
+static_assert(RF_NSEL == 0, "k_select<RlFill, RF_TOPIC> writes the count and clears the flags before RF_TOPIC");
 
 enum : int { PS_REACHED = 0, PS_ORPH, PS_LATMAX, PS_DEEP, PS_DELAY = 4, PS_CTO = 12, kPS = PS_CTO + GSIM_NET_CLASSES * GSIM_NET_CLASSES };
 
@@ -314,14 +251,7 @@ __global__ __launch_bounds__(kRlBlock) void k_relay_push(RelayArgs a)
     }
     if (CLS) {
         const uint32_t key = sc * GSIM_NET_CLASSES + mycls;
-        uint64_t todo = __ballot(other);
-        while (todo) {                                         // wave-uniform: the distinct (sender class, child class)
-            const int lead = __builtin_ctzll(todo);
-            const uint32_t kl = (uint32_t)__builtin_amdgcn_readlane((int)key, lead);
-            const uint64_t same = __ballot(other && key == kl);
-            if (lane == lead) atomicAdd(&s[PS_CTO + kl], (uint32_t)__popcll(same));
-            todo &= ~same;
-        }
+        count_keys(s + PS_CTO, other, key, lane);               // the distinct (sender class, child class)
     } else {
         const uint64_t m = __ballot(other);
         if (lane == 0 && m) atomicAdd(&s[PS_CTO], (uint32_t)__popcll(m));
@@ -403,6 +333,8 @@ __global__ __launch_bounds__(kRlBlock) void k_relay_fold(RelayArgs a)
         uint32_t* trow = s_acc + t * a.C * kRL;
         const uint32_t bin = c < GSIM_REPORT_BINS - 1 ? c : GSIM_REPORT_BINS - 1;
         const uint32_t key = mycls * GSIM_REPORT_BINS + bin;
+        // (written out: through lead_keys the fold measured 1.2 % slower than before, outside the
+        // spread of repeated runs)
         uint64_t todo = __ballot(held);
         while (todo) {                                         // wave-uniform: the distinct (class, fan-out bin) present
             const int lead = __builtin_ctzll(todo);
@@ -447,14 +379,10 @@ __global__ __launch_bounds__(kRlBlock) void k_relay_peers(RelayArgs a, const uin
     const uint64_t sub = active ? subs[p] : 0ull;
     const uint32_t mycls = CLS && active ? a.cls[p] : 0u;
     for (int32_t t = 0; t < a.T; ++t) {
-        uint64_t todo = __ballot((sub >> t) & 1ull);
-        while (todo) {                                         // wave-uniform: the classes present
-            const int lead = __builtin_ctzll(todo);
-            const uint32_t cl = (uint32_t)__builtin_amdgcn_readlane((int)mycls, lead);
-            const uint64_t same = __ballot(((sub >> t) & 1ull) && mycls == cl);
-            if (lane == lead) atomicAdd(&a.acc[((int64_t)t * a.C + cl) * kRC + RC_PEERS], (unsigned long long)__popcll(same));
-            todo &= ~same;
-        }
+        // the classes present
+        lead_keys((sub >> t) & 1ull, mycls, lane, [&](uint32_t cl, uint32_t cnt) {
+            atomicAdd(&a.acc[((int64_t)t * a.C + cl) * kRC + RC_PEERS], (unsigned long long)cnt);
+        });
     }
 }
 
@@ -512,23 +440,6 @@ __global__ __launch_bounds__(256) void k_relay_add(uint32_t* cnt, const uint32_t
     }
 }
 
-template <typename T>
-int grow(gsim_handle* h, T** p, int64_t* cap, int64_t need)
-{
-    if (*cap >= need) return GSIM_OK;
-    (void)hipStreamSynchronize(h->stream);
-    if (*p) (void)hipFree(*p);
-    *p = nullptr;
-    *cap = 0;
-    const hipError_t e = hipMalloc((void**)p, sizeof(T) * (size_t)need);
-    if (e != hipSuccess) {
-        h->err = std::string("relay report scratch: ") + hipGetErrorString(e);
-        return GSIM_ENOMEM;
-    }
-    *cap = need;
-    return GSIM_OK;
-}
-
 inline uint32_t peer_blocks(int64_t lo, int64_t hi)
 {
     const int64_t words = ((hi + 63) >> 6) - (lo >> 6);
@@ -544,9 +455,7 @@ void relayreport_release(gsim_handle* h)
 {
     if (!h->rl) return;
     RelayReport* r = h->rl;
-    void* all[] = {r->d_sel, r->d_flags, r->d_acc, r->d_macc, r->d_cnt, r->d_dep, r->d_inc, r->d_cto, r->d_rows};
-    for (void* p : all)
-        if (p) (void)hipFree(p);
+    free_all({r->d_sel, r->d_flags, r->d_acc, r->d_macc, r->d_cnt, r->d_dep, r->d_inc, r->d_cto, r->d_rows});
     delete r;
     h->rl = nullptr;
 }
@@ -567,26 +476,15 @@ int relay_begin(gsim_handle* h, int64_t round_lo, int64_t round_hi, int64_t* nse
     if (rc) return rc;
     if (!h->rl) h->rl = new RelayReport;
     RelayReport* r = h->rl;
-    hipError_t e = hipSuccess;
-    if (r->ring < v.ring) {
-        (void)hipStreamSynchronize(h->stream);
-        if (r->d_sel) (void)hipFree(r->d_sel);
-        if (r->d_macc) (void)hipFree(r->d_macc);
-        r->d_sel = nullptr;
-        r->d_macc = nullptr;
-        r->ring = 0;
-        e = hipMalloc((void**)&r->d_sel, sizeof(RlMsg) * (size_t)std::max<int32_t>(v.ring, 1));
-        if (e == hipSuccess) e = hipMalloc((void**)&r->d_macc, sizeof(uint32_t) * kRM * (size_t)std::max<int32_t>(v.ring, 1));
-        if (e == hipSuccess) r->ring = v.ring;
-    }
-    if (e == hipSuccess && !r->d_flags) e = hipMalloc((void**)&r->d_flags, sizeof(uint32_t) * kRF);
-    if (e == hipSuccess && !r->d_acc) e = hipMalloc((void**)&r->d_acc, sizeof(unsigned long long) * kRlAcc);
-    if (e != hipSuccess) {
-        h->err = std::string("relay report scratch: ") + hipGetErrorString(e);
-        return GSIM_ENOMEM;
-    }
-    hipLaunchKernelGGL(k_relay_select, dim3(1), dim3(kRlSelBlock), 0, h->stream, v, round_lo, round_hi, r->d_sel, r->d_flags);
-    e = hipGetLastError();
+    const int64_t slots = std::max<int32_t>(v.ring, 1);
+    rc = grow(h, kRlName, &r->d_sel, &r->sel_cap, slots);
+    if (!rc) rc = grow(h, kRlName, &r->d_macc, &r->macc_cap, slots * kRM);
+    if (!rc) rc = alloc_once(h, kRlName, &r->d_flags, kRF);
+    if (!rc) rc = alloc_once(h, kRlName, &r->d_acc, (int64_t)kRlAcc);
+    if (rc) return rc;
+    hipLaunchKernelGGL((k_select<RlFill, RF_TOPIC>), dim3(1), dim3(kSelBlock), 0, h->stream, v, round_lo, round_hi, r->d_sel,
+                       r->d_flags);
+    hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipMemcpyAsync(r->cs, r->d_flags, sizeof(r->cs), hipMemcpyDeviceToHost, h->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
     if (e != hipSuccess) return hip_check(h, e, "gsim_relay_report");
@@ -615,11 +513,11 @@ int relay_prepare(gsim_handle* h, int64_t B, int64_t olo, int64_t ohi, bool want
     r->want_cls = want_cls;
     r->want_msgs = want_msgs;
     const int64_t ent = r->B * a.n;
-    int rc = grow(h, &r->d_cnt, &r->slots_cap, ent);
-    if (!rc) rc = grow(h, &r->d_dep, &r->dep_cap, ent);
-    if (!rc && staged) rc = grow(h, &r->d_inc, &r->inc_cap, ent);
-    if (!rc && a.cls) rc = grow(h, &r->d_cto, &r->cto_cap, a.n * a.C);
-    if (!rc && r->want_peers) rc = grow(h, &r->d_rows, &r->rows_cap, ohi - olo);
+    int rc = grow(h, kRlName, &r->d_cnt, &r->slots_cap, ent);
+    if (!rc) rc = grow(h, kRlName, &r->d_dep, &r->dep_cap, ent);
+    if (!rc && staged) rc = grow(h, kRlName, &r->d_inc, &r->inc_cap, ent);
+    if (!rc && a.cls) rc = grow(h, kRlName, &r->d_cto, &r->cto_cap, a.n * a.C);
+    if (!rc && r->want_peers) rc = grow(h, kRlName, &r->d_rows, &r->rows_cap, ohi - olo);
     if (rc) return rc;
     a.cnt = r->d_cnt; a.dep = r->d_dep;
     a.cto = a.cls ? r->d_cto : nullptr;

@@ -15,9 +15,10 @@
 // owner exported, is counted once, by its owner.
 //
 // Launches per call (none per slot, no host loop over slots):
-//   k_report_select   one block: the slots published in [round_lo, round_hi),
-//                     compacted in slot order, each with its row header; the
-//                     rows' slot fields are the slot list of the next launch
+//   k_select<MsgFill> one block: the slots published in [round_lo, round_hi),
+//                     compacted in slot order (report_common.h), each with its
+//                     row header; the rows' slot fields are the slot list of the
+//                     next launch
 //   k_report_subs     subscribers per topic: a popcount pass over `sub` of the
 //                     owned peers
 //   k_report_reduce   block (x, y) reduces chunks x, x + gridDim.x, ... of
@@ -38,21 +39,21 @@
 // Resources (gfx950, -Rpass-analysis=kernel-resource-usage), none with scratch
 // or spills, all at 8 waves/SIMD:
 //   k_report_reduce  28 VGPRs, 54 SGPRs, 528 bytes of LDS
-//   k_report_select  24 VGPRs, 52 SGPRs, 68 bytes of LDS
+//   k_select<MsgFill>  24 VGPRs, 52 SGPRs, 68 bytes of LDS
 //   k_report_subs    10 VGPRs, 22 SGPRs, 1024 bytes of LDS
 // Measured: C3 after the default bench's ticks, 1477 messages,
 // 11.8 GB of cells in 2.20 ms for the whole call: 5.4 TB/s.
 #include <algorithm>
 #include <vector>
 
-#include "gsim_internal.h"
+#include "report_common.h"
 
 namespace gsim {
 
 struct Report {
     MsgReport* d_rows = nullptr;   // [ring] the selected rows, slot order
     uint32_t* d_cnt = nullptr;           // [0] selected rows, [1 + t] subscribers of topic t
-    int32_t ring = 0;
+    int64_t ring = 0;
 };
 
 namespace {
@@ -60,51 +61,22 @@ namespace {
 constexpr int kRpBlock = 256;            // k_report_reduce: 4 waves
 constexpr int kRpBatch = 4;              // 16-byte loads in flight per lane
 constexpr int kRpChunk = 2 * kRpBlock;   // cells a block reads per load step
-constexpr int kSelBlock = 1024;
 
-// The slots whose message was published in [lo, hi), compacted in slot order
-// (a block-wide prefix count per 1024 slots), with their row headers.
-__global__ __launch_bounds__(kSelBlock) void k_report_select(ReportView v, int64_t lo, int64_t hi, MsgReport* rows,
-                                                             uint32_t* cnt)
-{
-    __shared__ uint32_t s_w[kSelBlock / 64];
-    __shared__ uint32_t s_base;
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    if (tid == 0) s_base = 0;
-    __syncthreads();
-    for (int m0 = 0; m0 < v.ring; m0 += kSelBlock) {
-        const int m = m0 + tid;
-        bool sel = false;
-        int64_t pub = 0;
-        if (m < v.ring && v.slot_last[m] >= 0) {               // published at least once
-            pub = v.mpub[m];
-            sel = pub >= lo && pub < hi;
-        }
-        const uint64_t b = __ballot(sel);
-        if (lane == 0) s_w[w] = (uint32_t)__popcll(b);
-        __syncthreads();
-        uint32_t pos = s_base + (uint32_t)__popcll(b & ((1ull << lane) - 1ull));
-        for (int q = 0; q < w; ++q) pos += s_w[q];
-        if (sel) {
-            MsgReport& r = rows[pos];                     // hist, reached, max_latency: zeroed by the caller
-            r.id = v.mid[m];
-            r.pub_round = pub;
-            r.slot = (uint32_t)m;
-            r.topic = v.mtopic[m];
-            r.origin = v.morigin[m];
-            r.verdict = v.minv[m];
-            r.vdelay = v.mlat[m];
-        }
-        __syncthreads();
-        if (tid == 0) {
-            uint32_t tot = 0;
-            for (int q = 0; q < kSelBlock / 64; ++q) tot += s_w[q];
-            s_base += tot;
-        }
-        __syncthreads();
+// The selected slot's row header (k_select, report_common.h).
+struct MsgFill {
+    using Row = MsgReport;
+    __device__ static uint32_t fill(Row& r, const ReportView& v, int m, int64_t pub)
+    {
+        r.id = v.mid[m];                                       // hist, reached, max_latency: zeroed by the caller
+        r.pub_round = pub;
+        r.slot = (uint32_t)m;
+        r.topic = v.mtopic[m];
+        r.origin = v.morigin[m];
+        r.verdict = v.minv[m];
+        r.vdelay = v.mlat[m];
+        return r.topic;
     }
-    if (tid == 0) cnt[0] = s_base;
-}
+};
 
 // Subscribers per topic among the owned peers: lane t of a wave counts topic t.
 __global__ __launch_bounds__(256) void k_report_subs(const uint64_t* sub, int64_t rlo, int64_t rhi, int32_t T, uint32_t* out)
@@ -138,22 +110,19 @@ __device__ __forceinline__ void rp_add(uint32_t hi, uint32_t pub, int lane, uint
     const uint32_t d = hi - pub;
     const uint32_t bin = d < GSIM_REPORT_BINS - 1 ? d : GSIM_REPORT_BINS - 1;
     if (ok && d > mx) mx = d;
-    uint64_t todo = __ballot(ok);
-    while (todo) {                                             // wave-uniform
-        const int lead = __builtin_ctzll(todo);
-        const uint32_t b = (uint32_t)__builtin_amdgcn_readlane((int)bin, lead);
-        const uint64_t same = __ballot(ok && bin == b);
-        acc += lane == (int)b ? (uint32_t)__popcll(same) : 0u;
-        todo &= ~same;
-    }
+    walk_keys(ok, bin, [&](uint32_t b, uint64_t same, int) { acc += lane == (int)b ? (uint32_t)__popcll(same) : 0u; });
 }
 
 // members of topic t before peer p (a member-compacted topic; p <= n)
 __device__ __forceinline__ int64_t members_before(const Cells& cs, int32_t t, int64_t p, int64_t n, int64_t all)
 {
     if (p >= n) return all;
-    const int64_t i = (int64_t)t * cs.nw + (p >> 6);
-    return (int64_t)cs.mpre[i] + __popcll(cs.mbits[i] & ((1ull << (p & 63)) - 1ull));
+    uint64_t bits;
+    int64_t pre, idx;
+    bool has;
+    cs.word(t, p >> 6, bits, pre);
+    member_rank(bits, pre, (int)(p & 63), has, idx);            // (p itself need not be a member)
+    return idx;
 }
 
 __global__ __launch_bounds__(kRpBlock) void k_report_reduce(ReportView v, MsgReport* rows)
@@ -208,11 +177,7 @@ __global__ __launch_bounds__(kRpBlock) void k_report_reduce(ReportView v, MsgRep
         if (lane == 1 && b2 + 2 * np < e) hi = (uint32_t)(cell[e - 1] >> 32);
         rp_add(hi, pub, lane, acc, mx);
     }
-#pragma unroll
-    for (int o = 32; o; o >>= 1) {
-        const uint32_t x = (uint32_t)__shfl_xor((int)mx, o);
-        mx = x > mx ? x : mx;
-    }
+    mx = wave_max(mx);
     if (lane < GSIM_REPORT_BINS) s_h[w][lane] = acc;
     if (lane == 0) s_mx[w] = mx;
     __syncthreads();
@@ -238,28 +203,18 @@ using namespace gsim;
 void report_release(gsim_handle* h)
 {
     if (!h->rp) return;
-    if (h->rp->d_rows) (void)hipFree(h->rp->d_rows);
-    if (h->rp->d_cnt) (void)hipFree(h->rp->d_cnt);
+    free_all({h->rp->d_rows, h->rp->d_cnt});
     delete h->rp;
     h->rp = nullptr;
 }
 
 static int report_scratch(gsim_handle* h, int32_t ring)
 {
-    if (h->rp && h->rp->ring >= ring) return GSIM_OK;
-    (void)hipStreamSynchronize(h->stream);
-    report_release(h);
-    Report* r = new Report;
-    h->rp = r;
-    hipError_t e = hipMalloc((void**)&r->d_rows, sizeof(MsgReport) * (size_t)ring);
-    if (e == hipSuccess) e = hipMalloc((void**)&r->d_cnt, sizeof(uint32_t) * (1 + GSIM_MAX_TOPICS));
-    if (e != hipSuccess) {
-        report_release(h);
-        h->err = std::string("report scratch: ") + hipGetErrorString(e);
-        return GSIM_ENOMEM;
-    }
-    r->ring = ring;
-    return GSIM_OK;
+    if (!h->rp) h->rp = new Report;
+    Report* r = h->rp;
+    int rc = grow(h, "report", &r->d_rows, &r->ring, (int64_t)ring);
+    if (!rc) rc = alloc_once(h, "report", &r->d_cnt, 1 + GSIM_MAX_TOPICS);
+    return rc;
 }
 
 extern "C" {
@@ -281,7 +236,8 @@ int gsim_msg_report(gsim_handle* h, int64_t round_lo, int64_t round_hi, struct g
     if (fill) e = hipMemsetAsync(r->d_rows, 0, sizeof(MsgReport) * (size_t)v.ring, h->stream);
     if (e == hipSuccess) e = hipMemsetAsync(r->d_cnt, 0, sizeof(uint32_t) * (1 + GSIM_MAX_TOPICS), h->stream);
     if (e != hipSuccess) return hip_check(h, e, "gsim_msg_report");
-    hipLaunchKernelGGL(k_report_select, dim3(1), dim3(kSelBlock), 0, h->stream, v, round_lo, round_hi, r->d_rows, r->d_cnt);
+    hipLaunchKernelGGL((k_select<MsgFill, 0>), dim3(1), dim3(kSelBlock), 0, h->stream, v, round_lo, round_hi, r->d_rows,
+                       r->d_cnt);
     if (fill && v.rhi > v.rlo && v.T > 0)
         hipLaunchKernelGGL(k_report_subs, dim3((uint32_t)std::min<int64_t>(((int64_t)v.rhi - v.rlo + 255) / 256, 2048)),
                            dim3(256), 0, h->stream, v.sub, (int64_t)v.rlo, (int64_t)v.rhi, v.T, r->d_cnt + 1);

@@ -50,7 +50,7 @@
 #include <string>
 #include <vector>
 
-#include "gsim_internal.h"
+#include "report_common.h"
 
 namespace gsim {
 
@@ -70,12 +70,7 @@ constexpr size_t kSrMaxWords =
 struct ScoreReport {
     unsigned long long* d_acc = nullptr;                   // [kSrMaxWords] counters, topic flags, min / max keys
     gsim_topic_score_params* d_tp = nullptr;               // [T] what-if topic table
-    int32_t tp_cap = 0;
-};
-
-struct SrEdges {
-    double v[GSIM_NET_SCORE_BINS - 1];
-    int32_t n;
+    int64_t tp_cap = 0;
 };
 
 struct SrArgs {
@@ -92,7 +87,7 @@ struct SrArgs {
     int32_t T, C, sharded, mt_lazy;
     uint32_t olo, ohi;
     unsigned long long* acc;                               // [C^2 kSP] [T C^2 8] [C^2 10 2]
-    SrEdges ed;                                            // the total's histogram edges, by value
+    ScoreEdges ed;                                          // the total's histogram edges, by value
 };
 
 namespace {
@@ -124,20 +119,6 @@ __device__ __forceinline__ uint32_t sr_bin(double x)
     int m = (k + 8) >> 1;
     m = m < 0 ? 0 : (m > 15 ? 15 : m);
     return (u >> 63) ? (uint32_t)(15 - m) : (uint32_t)(17 + m);
-}
-
-// One key per lane of `on`: the wave's leader lanes add the popcounts of the
-// distinct keys present to the block's counters.  Called by the whole wave.
-__device__ __forceinline__ void count_keys(uint32_t* s_cnt, bool on, uint32_t key, int lane)
-{
-    uint64_t todo = __ballot(on);
-    while (todo) {                                         // wave-uniform
-        const int lead = __builtin_ctzll(todo);
-        const uint32_t k = (uint32_t)__builtin_amdgcn_readlane((int)key, lead);
-        const uint64_t same = __ballot(on && key == k);
-        if (lane == lead) atomicAdd(&s_cnt[k], (uint32_t)__popcll(same));
-        todo &= ~same;
-    }
 }
 
 template <bool Dense, bool CLS>
@@ -173,15 +154,11 @@ __global__ __launch_bounds__(kSrBlock) void k_score_report(SrArgs a_)
         // in a second word), so it keeps the wave's lanes of that pair
         uint64_t pmask0 = 0, pmask1 = 0;
         if (CLS) {
-            uint64_t todo = __ballot(conn);
-            while (todo) {                                 // wave-uniform: the distinct pairs present
-                const uint32_t k = (uint32_t)__builtin_amdgcn_readlane((int)pair, __builtin_ctzll(todo));
-                const uint64_t same = __ballot(conn && pair == k);
+            walk_keys(conn, pair, [&](uint32_t k, uint64_t same, int) {   // the distinct pairs present
                 if ((uint32_t)(lane >> 3) == (k & 7u)) {
                     if (k < 8u) pmask0 = same; else pmask1 = same;
                 }
-                todo &= ~same;
-            }
+            });
         } else {
             const uint64_t all = __ballot(conn);
             if (lane < kTopicFlags) pmask0 = all;
@@ -332,8 +309,7 @@ using namespace gsim;
 void scorereport_release(gsim_handle* h)
 {
     if (!h->sr) return;
-    if (h->sr->d_acc) (void)hipFree(h->sr->d_acc);
-    if (h->sr->d_tp) (void)hipFree(h->sr->d_tp);
+    free_all({h->sr->d_acc, h->sr->d_tp});
     delete h->sr;
     h->sr = nullptr;
 }
@@ -356,19 +332,8 @@ int gsim_score_report(gsim_handle* h, const struct gsim_score_what_if* what_if, 
     *n_topics = nt;
     if (hipSetDevice(h->device) != hipSuccess) return GSIM_EDEVICE;
     if (h->e == 0 && h->n == 0) { h->err = "no graph loaded (call gsim_load_graph first)"; return GSIM_ESTATE; }
-    if (n_edges < 0 || n_edges > GSIM_NET_SCORE_BINS - 1 || (n_edges > 0 && !edges)) {
-        h->err = "gsim_score_report: n_edges must lie in 0..15";
-        return GSIM_EINVAL;
-    }
-    SrEdges ed{};
-    ed.n = n_edges;
-    for (int k = 0; k < n_edges; ++k) {
-        if (edges[k] != edges[k] || (k > 0 && !(edges[k] > edges[k - 1]))) {
-            h->err = "gsim_score_report: the edges must be strictly ascending, without NaN";
-            return GSIM_EINVAL;
-        }
-        ed.v[k] = edges[k];
-    }
+    ScoreEdges ed{};
+    if (int rc = score_edges(h, "gsim_score_report", edges, n_edges, &ed)) return rc;
     // what-if parameters: validated as the engine's own were
     const gsim_peer_score_params* pp = &h->pp;
     const gsim_topic_score_params* wtp = nullptr;
@@ -404,19 +369,12 @@ int gsim_score_report(gsim_handle* h, const struct gsim_score_what_if* what_if, 
     if (rc) return rc;
     if (!h->sr) h->sr = new ScoreReport;
     ScoreReport* s = h->sr;
-    hipError_t e = hipSuccess;
-    if (!s->d_acc) e = hipMalloc((void**)&s->d_acc, sizeof(unsigned long long) * kSrMaxWords);
-    if (e == hipSuccess && wtp && s->tp_cap < T) {
-        if (s->d_tp) (void)hipFree(s->d_tp);
-        s->d_tp = nullptr;
-        s->tp_cap = 0;
-        e = hipMalloc((void**)&s->d_tp, sizeof(gsim_topic_score_params) * (size_t)T);
-        if (e == hipSuccess) s->tp_cap = T;
-    }
-    if (e != hipSuccess) { h->err = std::string("report scratch: ") + hipGetErrorString(e); return GSIM_ENOMEM; }
+    rc = alloc_once(h, "report", &s->d_acc, (int64_t)kSrMaxWords);
+    if (!rc && wtp) rc = grow(h, "report", &s->d_tp, &s->tp_cap, (int64_t)T);
+    if (rc) return rc;
     const size_t n_cnt = (size_t)npairs * kSP, n_top = (size_t)nt * kTopicFlags, n_mm = (size_t)np * 2;
     const size_t words = n_cnt + n_top + n_mm;
-    e = hipMemsetAsync(s->d_acc, 0, sizeof(unsigned long long) * words, h->stream);
+    hipError_t e = hipMemsetAsync(s->d_acc, 0, sizeof(unsigned long long) * words, h->stream);
     // (the engine's d_tp is never written: the what-if table has its own)
     if (e == hipSuccess && wtp)
         e = hipMemcpyAsync(s->d_tp, wtp, sizeof(gsim_topic_score_params) * (size_t)T, hipMemcpyHostToDevice, h->stream);

@@ -38,11 +38,6 @@
 
 #include "gsim.h"
 #include "gsim_internal.h"
-#include "meshpaths_merge.h"
-#include "relayreport_merge.h"
-#include "netreport_merge.h"
-#include "scorereport_merge.h"
-#include "peerreport_merge.h"
 #include "report_merge.h"
 #include "shard_layout.h"
 
@@ -1357,6 +1352,28 @@ int group_create(const gsim_peer_score_params* params, const gsim_topic_score_pa
     return GSIM_OK;
 }
 
+// One row kind of a group report: every local shard's n rows and the pointer
+// list a merge takes (report_merge.h).  A kind the caller does not want holds
+// nothing and hands out nullptr and a capacity of 0 throughout.
+template <typename Row>
+struct ShardRows {
+    bool want;
+    int64_t n;
+    std::vector<std::vector<Row>> part;
+    std::vector<const Row*> ptr;
+    ShardRows(size_t shards, bool want_, int64_t n_) : want(want_), n(n_), part(shards) {}
+    Row* buf(size_t l)                          // shard l's rows, once per shard, in shard order
+    {
+        if (!want) return nullptr;
+        part[l].resize((size_t)n);
+        ptr.push_back(part[l].data());
+        return part[l].data();
+    }
+    int64_t cap() const { return want ? n : 0; }
+    const Row* const* parts() const { return want ? ptr.data() : nullptr; }
+    Row* out(Row* o) const { return want ? o : nullptr; }
+};
+
 }  // namespace
 
 extern "C" {
@@ -2207,23 +2224,18 @@ int gsim_group_msg_report(gsim_group* g, int64_t round_lo, int64_t round_hi, str
     *n = cnt;
     if (!out || cap == 0) return GSIM_OK;
     if (cap < cnt) return g->fail(GSIM_ERANGE, "output buffer too small for the selected messages");
-    std::vector<std::vector<MsgReport>> parts(g->hs.size());
-    for (size_t l = 0; l < g->hs.size(); ++l) {
-        parts[l].resize((size_t)cnt);
-        int64_t got = 0;
-        rc = cnt ? call(g->hs[l], parts[l].data(), cnt, &got) : call(g->hs[l], nullptr, 0, &got);
-        if (rc) return rc;
-        if (got != cnt) return g->fail(GSIM_ESTATE, "the shards disagree about the messages in the ring");
-    }
-    std::vector<const MsgReport*> pp;
+    ShardRows<MsgReport> rows(g->hs.size(), true, cnt);
     std::vector<const uint32_t*> gp;
     std::vector<size_t> gn;
     for (size_t l = 0; l < g->hs.size(); ++l) {
-        pp.push_back(parts[l].data());
+        int64_t got = 0;
+        rc = call(g->hs[l], rows.buf(l), rows.cap(), &got);     // (no message selected: a count-only call)
+        if (rc) return rc;
+        if (got != cnt) return g->fail(GSIM_ESTATE, "the shards disagree about the messages in the ring");
         gp.push_back(g->gid[l].data());
         gn.push_back(g->gid[l].size());
     }
-    if (merge_reports(pp.data(), gp.data(), gn.data(), pp.size(), (size_t)cnt, out))
+    if (merge_reports(rows.parts(), gp.data(), gn.data(), g->hs.size(), (size_t)cnt, out))
         return g->fail(GSIM_ESTATE, "the shards disagree about a slot's message");
     return GSIM_OK;
 }
@@ -2256,7 +2268,7 @@ int gsim_group_set_peer_classes(gsim_group* g, const uint8_t* cls)
 }
 
 // gsim_net_report over the group: every local shard reports the observers it
-// owns; the rows are merged on the host (netreport_merge.cpp).
+// owns; the rows are merged on the host (report_merge.cpp).
 int gsim_group_net_report(gsim_group* g, const double* edges, int32_t n_edges, struct gsim_mesh_row* mesh,
                           int64_t mesh_cap, int64_t* n_mesh, struct gsim_score_row* scores, int64_t score_cap,
                           int64_t* n_scores)
@@ -2274,23 +2286,15 @@ int gsim_group_net_report(gsim_group* g, const double* edges, int32_t n_edges, s
         return g->fail(GSIM_ERANGE, "gsim_group_net_report: output buffer too small");
     if (!want_mesh && !want_scores) return GSIM_OK;
     const size_t L = g->hs.size();
-    std::vector<std::vector<gsim_mesh_row>> mp(L);
-    std::vector<std::vector<gsim_score_row>> sp(L);
-    std::vector<const gsim_mesh_row*> mpp;
-    std::vector<const gsim_score_row*> spp;
+    ShardRows<gsim_mesh_row> mr(L, want_mesh, nm);
+    ShardRows<gsim_score_row> sr(L, want_scores, ns);
     for (size_t l = 0; l < L; ++l) {
-        if (want_mesh) mp[l].resize((size_t)nm);
-        if (want_scores) sp[l].resize((size_t)ns);
         int64_t gm = 0, gs = 0;
-        rc = gsim_net_report(g->hs[l], edges, n_edges, want_mesh ? mp[l].data() : nullptr, want_mesh ? nm : 0, &gm,
-                             want_scores ? sp[l].data() : nullptr, want_scores ? ns : 0, &gs);
+        rc = gsim_net_report(g->hs[l], edges, n_edges, mr.buf(l), mr.cap(), &gm, sr.buf(l), sr.cap(), &gs);
         if (rc) return g->take(g->hs[l], rc);
         if (gm != nm || gs != ns) return g->fail(GSIM_ESTATE, "the shards disagree about the report's rows");
-        mpp.push_back(mp[l].data());
-        spp.push_back(sp[l].data());
     }
-    if (merge_net_reports(want_mesh ? mpp.data() : nullptr, want_scores ? spp.data() : nullptr, L, (size_t)nm, (size_t)ns,
-                          want_mesh ? mesh : nullptr, want_scores ? scores : nullptr))
+    if (merge_net_reports(mr.parts(), sr.parts(), L, (size_t)nm, (size_t)ns, mr.out(mesh), sr.out(scores)))
         return g->fail(GSIM_ESTATE, "the shards disagree about a report row's key");
     return GSIM_OK;
 }
@@ -2298,7 +2302,7 @@ int gsim_group_net_report(gsim_group* g, const double* edges, int32_t n_edges, s
 // gsim_score_report over the group: every local shard reports the records of
 // the observers it owns under the same what-if parameters (a ghost subject
 // carries its class and its app-specific score); the rows are merged on the
-// host (scorereport_merge.cpp).
+// host (report_merge.cpp).
 int gsim_group_score_report(gsim_group* g, const struct gsim_score_what_if* what_if, const double* edges, int32_t n_edges,
                             struct gsim_score_part_row* parts, int64_t part_cap, int64_t* n_parts,
                             struct gsim_score_cause_row* causes, int64_t cause_cap, int64_t* n_causes,
@@ -2319,36 +2323,25 @@ int gsim_group_score_report(gsim_group* g, const struct gsim_score_what_if* what
         return g->fail(GSIM_ERANGE, "gsim_group_score_report: output buffer too small");
     if (!want_parts && !want_causes && !want_topics) return GSIM_OK;
     const size_t L = g->hs.size();
-    std::vector<std::vector<gsim_score_part_row>> pp(L);
-    std::vector<std::vector<gsim_score_cause_row>> cp(L);
-    std::vector<std::vector<gsim_score_topic_row>> tp(L);
-    std::vector<const gsim_score_part_row*> ppp;
-    std::vector<const gsim_score_cause_row*> cpp;
-    std::vector<const gsim_score_topic_row*> tpp;
+    ShardRows<gsim_score_part_row> pr(L, want_parts, np);
+    ShardRows<gsim_score_cause_row> cr(L, want_causes, nc);
+    ShardRows<gsim_score_topic_row> tr(L, want_topics, nt);
     for (size_t l = 0; l < L; ++l) {
-        if (want_parts) pp[l].resize((size_t)np);
-        if (want_causes) cp[l].resize((size_t)nc);
-        if (want_topics) tp[l].resize((size_t)nt);
         int64_t gp = 0, gc = 0, gt = 0;
-        rc = gsim_score_report(g->hs[l], what_if, edges, n_edges, want_parts ? pp[l].data() : nullptr, want_parts ? np : 0,
-                               &gp, want_causes ? cp[l].data() : nullptr, want_causes ? nc : 0, &gc,
-                               want_topics ? tp[l].data() : nullptr, want_topics ? nt : 0, &gt);
+        rc = gsim_score_report(g->hs[l], what_if, edges, n_edges, pr.buf(l), pr.cap(), &gp, cr.buf(l), cr.cap(), &gc,
+                               tr.buf(l), tr.cap(), &gt);
         if (rc) return g->take(g->hs[l], rc);
         if (gp != np || gc != nc || gt != nt) return g->fail(GSIM_ESTATE, "the shards disagree about the report's rows");
-        ppp.push_back(pp[l].data());
-        cpp.push_back(cp[l].data());
-        tpp.push_back(tp[l].data());
     }
-    if (merge_score_reports(want_parts ? ppp.data() : nullptr, want_causes ? cpp.data() : nullptr,
-                            want_topics ? tpp.data() : nullptr, L, (size_t)np, (size_t)nc, (size_t)nt,
-                            want_parts ? parts : nullptr, want_causes ? causes : nullptr, want_topics ? topics : nullptr))
+    if (merge_score_reports(pr.parts(), cr.parts(), tr.parts(), L, (size_t)np, (size_t)nc, (size_t)nt, pr.out(parts),
+                            cr.out(causes), tr.out(topics)))
         return g->fail(GSIM_ESTATE, "the shards disagree about a report row's key");
     return GSIM_OK;
 }
 
 // gsim_peer_report over the group: every local shard reports the peers it
 // owns, in its local ids; the per-peer rows land at the peers' global ids and
-// the class rows are merged on the host (peerreport_merge.cpp).  An owned
+// the class rows are merged on the host (report_merge.cpp).  An owned
 // peer's committed cell names its first sender by a local id of the shard
 // (owned or ghost, peerreport.hip) and the shard's class array covers its
 // ghosts, so a first sender owned by another shard counts under its class.
@@ -2370,8 +2363,7 @@ int gsim_group_peer_report(gsim_group* g, int64_t round_lo, int64_t round_hi, in
     if (want_cls && class_cap < nc) return g->fail(GSIM_ERANGE, "gsim_group_peer_report: class row buffer too small");
     if (!want_cls && !want_peers) return GSIM_OK;
     const size_t L = g->hs.size();
-    std::vector<std::vector<gsim_peer_class_row>> parts(L);
-    std::vector<const gsim_peer_class_row*> pp;
+    ShardRows<gsim_peer_class_row> cr(L, want_cls, nc);
     std::vector<int64_t> got(L, 0);
     for (size_t l = 0; l < L; ++l) {
         gsim_handle* h = g->hs[l];
@@ -2381,15 +2373,13 @@ int gsim_group_peer_report(gsim_group* g, int64_t round_lo, int64_t round_hi, in
         const int64_t lo = std::max(peer_lo, g->bounds[(size_t)k]), hi = std::min(peer_hi, g->bounds[(size_t)k + 1]);
         const bool rows = want_peers && lo < hi;
         const int64_t llo = rows ? sc->own_lo + (lo - g->bounds[(size_t)k]) : 0, lhi = rows ? llo + (hi - lo) : 0;
-        if (want_cls) parts[l].resize((size_t)nc);
         int64_t gc = 0;
-        rc = gsim_peer_report(h, round_lo, round_hi, llo, lhi, rows ? peers + (lo - peer_lo) : nullptr,
-                              want_cls ? parts[l].data() : nullptr, want_cls ? nc : 0, &gc, &got[l]);
+        rc = gsim_peer_report(h, round_lo, round_hi, llo, lhi, rows ? peers + (lo - peer_lo) : nullptr, cr.buf(l), cr.cap(),
+                              &gc, &got[l]);
         if (rc) return g->take(h, rc);
         if (gc != nc || got[l] != cnt) return g->fail(GSIM_ESTATE, "the shards disagree about the report's rows or messages");
-        pp.push_back(parts[l].data());
     }
-    if (want_cls && merge_peer_reports(pp.data(), got.data(), L, (size_t)nc, classes))
+    if (want_cls && merge_peer_reports(cr.parts(), got.data(), L, (size_t)nc, classes))
         return g->fail(GSIM_ESTATE, "the shards disagree about a class row's key or messages");
     return GSIM_OK;
 }
@@ -2401,7 +2391,7 @@ int gsim_group_peer_report(gsim_group* g, int64_t round_lo, int64_t round_hi, in
 // translated to their owners' local ids (gid) and added there, and every owner
 // folds the total children of its own peers.  The children by class of a ghost
 // sender reach its owner's row on the host at the end; the class rows are merged
-// on the host (relayreport_merge.cpp).
+// on the host (report_merge.cpp).
 int gsim_group_relay_report(gsim_group* g, int64_t round_lo, int64_t round_hi, int64_t peer_lo, int64_t peer_hi,
                             struct gsim_relay_row* peers, struct gsim_relay_class_row* classes, int64_t class_cap,
                             int64_t* n_classes, int64_t* n_msgs)
@@ -2524,7 +2514,7 @@ int gsim_group_relay_report(gsim_group* g, int64_t round_lo, int64_t round_hi, i
 // the frontier of its owned peers over its own rows; between the push and the
 // fold of a level the bits that landed on ghosts are read from every shard,
 // translated to global ids (gid) and ORed into the owner's fold.  The rows are
-// summed on the host (meshpaths_merge.cpp); the per-peer arrays land at the
+// summed on the host (report_merge.cpp); the per-peer arrays land at the
 // owned peers' global ids.
 int gsim_group_mesh_paths(gsim_group* g, int32_t topic, const uint32_t* sources, int32_t n_sources, uint32_t blocked,
                           int32_t max_hops, struct gsim_mesh_path_row* rows, uint32_t* reach_count, uint32_t* hop_sum)

@@ -34,7 +34,8 @@ from gsim.params import Second
 from gsim.presets import beacon_params
 from test_delivery import R, T0
 from test_heartbeat import SEED, tick_time
-from test_msg_report import GP, TH, VERDICTS, compact_case, cycle_network, dense_case, fixed_schedule, lockstep
+from test_msg_report import (GP, TH, VERDICTS, WIDE_RING, WIDE_WINDOWS, compact_case, cycle_network, dense_case,
+                             fixed_schedule, lockstep, wide_ring_case)
 
 BINS = _abi.REPORT_BINS
 NC = _abi.NET_CLASSES
@@ -117,15 +118,15 @@ def test_peer_report_helpers_on_hand_written_rows():
 
 
 def test_peer_report_merge_under_host_sanitizers(tmp_path):
-    """The host-side merge of the shards' class rows (csrc/peerreport_merge.cpp)
+    """The host-side merge of the shards' class rows (csrc/report_merge.cpp)
     built into a stand-alone program with AddressSanitizer and UBSan and run:
     sums, maxima, disagreeing keys, messages and selected counts refused."""
-    exe = tmp_path / "peerreport_merge_check"
+    exe = tmp_path / "report_merge_check"
     subprocess.check_call(["g++", "-std=c++17", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
                            "-I", os.path.join(REPO, "include"), "-I", os.path.join(REPO, "go-libp2p-pubsub_amd", "csrc"),
-                           os.path.join(REPO, "tools", "peerreport_merge_check.cpp"),
-                           os.path.join(REPO, "go-libp2p-pubsub_amd", "csrc", "peerreport_merge.cpp"), "-o", str(exe)])
-    out = subprocess.run([str(exe)], capture_output=True, text=True)
+                           os.path.join(REPO, "tools", "report_merge_check.cpp"),
+                           os.path.join(REPO, "go-libp2p-pubsub_amd", "csrc", "report_merge.cpp"), "-o", str(exe)])
+    out = subprocess.run([str(exe), "peer"], capture_output=True, text=True)
     assert out.returncode == 0 and "peer report merge ok" in out.stdout, out.stdout + out.stderr
 
 
@@ -257,9 +258,10 @@ def assert_class_rows(got, want, any_pending, where=""):
         assert (ff == wf).all(), f"{where}: class first_from differs: {ff.tolist()} vs {wf.tolist()}"
 
 
-def run_with_peer_report(make_engine, net, params, st, ticks, sched, cls=None, after=None, **kw):
+def run_with_peer_report(make_engine, net, params, st, ticks, sched, cls=None, after=None, windows=(), **kw):
     """run_parity on an engine of the test's; the oracle's event log runs from
-    before the first round and the report is checked after every tick.
+    before the first round and the report is checked after every tick (the
+    whole ring, then every round window of `windows`).
     after(kk, eng, got, want, pending, sel): the test's own checks per tick."""
     from tickrun import run_parity
     eng = make_engine()
@@ -284,6 +286,11 @@ def run_with_peer_report(make_engine, net, params, st, ticks, sched, cls=None, a
         got_p, got_c = eng.peer_report()
         assert_peer_rows(got_p, want_p, pending, f"tick {kk}")
         assert_class_rows(got_c, want_c, bool(pending.any()), f"tick {kk}")
+        for lo, hi in windows:
+            w_p, w_c, w_pending, _ = expected_peer_report(msgs, st_, first, cls, C, lo, hi)
+            g_p, g_c = eng.peer_report(lo, hi)
+            assert_peer_rows(g_p, w_p, w_pending, f"tick {kk} [{lo}, {hi})")
+            assert_class_rows(g_c, w_c, bool(w_pending.any()), f"tick {kk} [{lo}, {hi})")
         state["ticks"] += 1
         state["pending"].append(int(sel["pending"].sum()))
         if after:
@@ -432,6 +439,26 @@ def test_peer_report_slot_split(require_gpu):
     run_with_peer_report(lambda: Engine(params, TH, gossip=GP), net, params, st, ticks, sched, cls=cls, after=after, ring=512)
     assert sum(len(b) for b in sched.values()) == 40
     assert parts[-1] > 1 and parts[0] == 1, f"the slots of the last ticks must be split: {parts}"
+
+
+@pytest.mark.gpu
+def test_peer_report_ring_past_one_selection_pass(require_gpu):
+    """A ring of 2048 slots (test_msg_report.wide_ring_case): the whole ring and
+    each tick's window select slots below and from 1024 on, so the second
+    selection pass appends behind the first's rows and adds to its per-topic
+    message counts."""
+    net, params, st, ticks, sched = wide_ring_case()
+    cls = (np.arange(net.n) % 3).astype(np.uint8)
+    seen = []
+
+    def after(kk, eng, got, want, pending, sel, msgs):
+        seen.append((sel["idx"].tolist(), got[1]["messages"].tolist()))
+
+    run_with_peer_report(lambda: Engine(params, TH, gossip=GP), net, params, st, ticks, sched, cls=cls, after=after,
+                         windows=WIDE_WINDOWS, ring=WIDE_RING)
+    idx, messages = seen[-1]
+    assert idx == [3, 1023, 1024, 1500, 2047]
+    assert messages == [3, 3, 3, 2, 2, 2], "topic 0: ids 3, 2047, 1500; topic 1: ids 1024, 1023"
 
 
 @pytest.mark.gpu

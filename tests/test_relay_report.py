@@ -40,7 +40,8 @@ from gsim.presets import beacon_params
 from test_delivery import R, T0
 from test_gossip import cut_mesh, gossip_net
 from test_heartbeat import SEED, tick_time
-from test_msg_report import GP, TH, VERDICTS, compact_case, cycle_network, dense_case, fixed_schedule, lockstep, vdelays_of
+from test_msg_report import (GP, TH, VERDICTS, WIDE_RING, WIDE_WINDOWS, compact_case, cycle_network, dense_case,
+                             fixed_schedule, lockstep, vdelays_of, wide_ring_case)
 from test_peer_report import FirstSenders, three_classes
 
 BINS = _abi.REPORT_BINS
@@ -208,12 +209,12 @@ def oracle_ticks(net, st, ticks, sched, ring=64, topic_slots=0, before_round=Non
         yield kk, msgs, first
 
 
-def run_with_relay_report(make_engine, net, params, st, ticks, sched, cls=None, after=None, quiet=1, **kw):
+def run_with_relay_report(make_engine, net, params, st, ticks, sched, cls=None, after=None, quiet=1, windows=(), **kw):
     """run_parity on an engine of the test's with `quiet` more ticks without
     publications (one; two where a validation latency of 2 makes a hop take three
     rounds, test_relay_schedules_keep_the_pending_condition); the oracle's event
     log runs from before the first round and the report is checked after every
-    tick.  after(kk, eng, got, want, sel, msgs): the test's own checks per tick.
+    tick (the whole ring, then every round window of `windows`).  after(kk, eng, got, want, sel, msgs): the test's own checks per tick.
     Returns the run's state, "last": the last tick's (got, want, sel)."""
     from tickrun import run_parity
     ticks = list(ticks) + [max(ticks) + 1 + q for q in range(quiet)]
@@ -240,6 +241,9 @@ def run_with_relay_report(make_engine, net, params, st, ticks, sched, cls=None, 
         want_p, want_c, want_m, sel = expected_relay_report(msgs, st_.net.sub, st_.T, first, cls, C, vd)
         got = eng.relay_report()
         assert_relay(got, (want_p, want_c, want_m), sel, f"tick {kk}")
+        for lo, hi in windows:
+            w_p, w_c, w_m, w_sel = expected_relay_report(msgs, st_.net.sub, st_.T, first, cls, C, vd, lo, hi)
+            assert_relay(eng.relay_report(lo, hi), (w_p, w_c, w_m), w_sel, f"tick {kk} [{lo}, {hi})")
         state["ticks"] += 1
         state["pending"].append(int(sel["pending"].sum()))
         state["last"] = (got, (want_p, want_c, want_m), sel)
@@ -340,15 +344,15 @@ def test_relay_report_helpers_on_hand_written_rows():
 
 
 def test_relay_report_merge_under_host_sanitizers(tmp_path):
-    """The host-side merge of the shards' class rows (csrc/relayreport_merge.cpp)
+    """The host-side merge of the shards' class rows (csrc/report_merge.cpp)
     built into a stand-alone program with AddressSanitizer and UBSan and run:
     sums, maxima, disagreeing keys, messages and selected counts refused."""
-    exe = tmp_path / "relayreport_merge_check"
+    exe = tmp_path / "report_merge_check"
     subprocess.check_call(["g++", "-std=c++17", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
                            "-I", os.path.join(REPO, "include"), "-I", os.path.join(REPO, "go-libp2p-pubsub_amd", "csrc"),
-                           os.path.join(REPO, "tools", "relayreport_merge_check.cpp"),
-                           os.path.join(REPO, "go-libp2p-pubsub_amd", "csrc", "relayreport_merge.cpp"), "-o", str(exe)])
-    out = subprocess.run([str(exe)], capture_output=True, text=True)
+                           os.path.join(REPO, "tools", "report_merge_check.cpp"),
+                           os.path.join(REPO, "go-libp2p-pubsub_amd", "csrc", "report_merge.cpp"), "-o", str(exe)])
+    out = subprocess.run([str(exe), "relay"], capture_output=True, text=True)
     assert out.returncode == 0 and "relay report merge ok" in out.stdout, out.stdout + out.stderr
 
 
@@ -484,6 +488,22 @@ def test_relay_report_member_compacted(require_gpu):
     two = gm_[(gm_["vdelay"] == 2) & (gm_["reached"] > 100)]
     assert len(two) and (two["delay_hist"][:, :2].sum(axis=1) == 0).all(), "with vdelay 2 every hop takes 3 rounds or more"
     assert not gm_["orphans"].any()
+
+
+@pytest.mark.gpu
+def test_relay_report_ring_past_one_selection_pass(require_gpu):
+    """A ring of 2048 slots (test_msg_report.wide_ring_case): the whole ring and
+    each tick's window select slots below and from 1024 on, so the second
+    selection pass appends behind the first's rows and adds to its per-topic
+    message counts."""
+    net, params, st, ticks, sched = wide_ring_case()
+    cls = (np.arange(net.n) % 3).astype(np.uint8)
+    state = run_with_relay_report(lambda: Engine(params, TH, gossip=GP), net, params, st, ticks, sched, cls=cls,
+                                  windows=WIDE_WINDOWS, ring=WIDE_RING)
+    (gp_, gc_, gm_), _, _ = state["last"]
+    assert gm_["slot"].tolist() == [3, 1024, 2047, 1023, 1500], "ordered by (pub_round, slot)"
+    assert gc_["messages"].tolist() == [3, 3, 3, 2, 2, 2], "topic 0: ids 3, 2047, 1500; topic 1: ids 1024, 1023"
+    assert (gm_["reached"] > 100).sum() >= 3 and not gm_["orphans"].any()     # (id 2047 is rejected: it stays near its origin)
 
 
 @pytest.mark.gpu

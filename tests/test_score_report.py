@@ -163,15 +163,15 @@ def test_score_report_helpers_on_hand_written_rows():
 
 
 def test_score_report_merge_under_host_sanitizers(tmp_path):
-    """The host-side merge of the shards' rows (csrc/scorereport_merge.cpp) built
+    """The host-side merge of the shards' rows (csrc/report_merge.cpp) built
     into a stand-alone program with AddressSanitizer and UBSan and run: sums,
     the min / max identities, disagreeing keys refused."""
-    exe = tmp_path / "scorereport_merge_check"
+    exe = tmp_path / "report_merge_check"
     subprocess.check_call(["g++", "-std=c++17", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
                            "-I", os.path.join(REPO, "include"), "-I", os.path.join(REPO, "go-libp2p-pubsub_amd", "csrc"),
-                           os.path.join(REPO, "tools", "scorereport_merge_check.cpp"),
-                           os.path.join(REPO, "go-libp2p-pubsub_amd", "csrc", "scorereport_merge.cpp"), "-o", str(exe)])
-    out = subprocess.run([str(exe)], capture_output=True, text=True)
+                           os.path.join(REPO, "tools", "report_merge_check.cpp"),
+                           os.path.join(REPO, "go-libp2p-pubsub_amd", "csrc", "report_merge.cpp"), "-o", str(exe)])
+    out = subprocess.run([str(exe), "score"], capture_output=True, text=True)
     assert out.returncode == 0 and "score report merge ok" in out.stdout, out.stdout + out.stderr
 
 
