@@ -62,6 +62,7 @@ __device__ __forceinline__ bool bit128(uint64_t w0, uint64_t w1, int k)
 }
 
 // seen-set cell encoding: kUnseen64, kClaim, ... (gsim_internal.h)
+constexpr int64_t kMaxPromTicks = 64;   // promise ring indices (gsim_msgs_init refuses a clock that needs more)
 constexpr int kMaxRing = 8192;     // active-slot list lives in LDS (u16, sized by the ring)
 
 // The verdict of a message (gsim.h GSIM_VERDICT_*, stored in minv[slot]):
@@ -215,6 +216,7 @@ struct Deliver {
     std::vector<int64_t> prom_made;    // [P] tick that filled each ring index, -1 = empty
     int64_t ihave_tick = -1;           // heartbeat whose IHAVE marks are pending
     int64_t resp_round = -1;           // round in which the queued responses arrive
+    bool resp_marked = false;          // the queued responses carry kRespWasUp (a connection changed since)
 };
 
 constexpr uint32_t kMcntSpill = 128;    // pending mesh-delivery increments a record's byte holds (atomic_mcnt_inc)
@@ -3314,8 +3316,24 @@ __global__ __launch_bounds__(256) void k_flist_fresh(RoundArgs a, int only_bad)
 // Copies that arrive as a list of (record, slot): round 2's messages queued by
 // handleIWant (a shard's copies pushed by other shards arrive as bits:
 // k_xbits_deliver).  Same rules and tracer events as k_send_tm's copies.
+constexpr uint64_t kRespWasUp = 1ull << 63;   // a queued answer: its connection was up when it was sent
+
+// Before connections change while answers are queued (churn or the PX connector
+// between a tick's handleIWant and the next tick's round 0): each answer
+// records whether the receiver's connection to its sender is up now, as it
+// was when the answer was sent.
+__global__ __launch_bounds__(256) void k_resp_mark(uint64_t* resp, const uint32_t* nresp, int64_t resp_cap,
+                                                   const uint32_t* rev, const uint8_t* rstate)
+{
+    const uint32_t n = (uint32_t)min((int64_t)*nresp, resp_cap);
+    for (uint32_t x = blockIdx.x * blockDim.x + threadIdx.x; x < n; x += gridDim.x * blockDim.x) {
+        const uint64_t ent = resp[x];
+        if (rstate[rev[(uint32_t)ent]] & GSIM_ES_CONNECTED) resp[x] = ent | kRespWasUp;
+    }
+}
+
 __global__ __launch_bounds__(256) void k_gossip_deliver(RoundArgs a_, const uint64_t* resp, const uint32_t* nresp,
-                                                       const uint32_t* owner, int64_t resp_cap)
+                                                       const uint32_t* owner, int64_t resp_cap, int lost_check)
 {
     const RoundArgs& a = a_;
     extern __shared__ uint32_t s_new2[];
@@ -3333,7 +3351,12 @@ __global__ __launch_bounds__(256) void k_gossip_deliver(RoundArgs a_, const uint
     for (uint32_t x = blockIdx.x * blockDim.x + threadIdx.x; x < n; x += gridDim.x * blockDim.x) {
         const RoundArgs& a = kernarg0(a_);   // (re-read per copy: SGPR pressure)
         const uint64_t ent = resp[x];
-        const uint32_t r = (uint32_t)ent, m = (uint32_t)(ent >> 32);
+        const uint32_t r = (uint32_t)ent, m = (uint32_t)((ent & ~kRespWasUp) >> 32);
+        // an answer whose connection was up when handleIWant sent it and has gone down
+        // since (churn between two ticks, when a tick's last rounds queue for the next) is
+        // lost with its stream: sent, never received.  r is the sender's
+        // edge, rev[r] the receiver's own; no connection changed since: nothing to test
+        const bool up = !(lost_check && (ent & kRespWasUp) && !(a.dstate[a.rev[r]] & GSIM_DS_CONNECTED));
         if (a.tr.ev) {
             // the IWANT answer's RPC (a single engine: every entry is one), sent by
             // handleIWant in the round before it arrives (trace.go:250-297)
@@ -3341,8 +3364,9 @@ __global__ __launch_bounds__(256) void k_gossip_deliver(RoundArgs a_, const uint
             const int32_t rt = (int32_t)a.mtopic[m];
             // (a ghost advertiser's answers are known only at the requester's shard)
             if (a.tr.on_any(rs)) a.tr.push(round_time(a, a.g - 1), ((uint64_t)a.g << 32) | m, rs, rp, rt, GSIM_TRACE_SEND_RPC, 1);
-            if (a.tr.on(rp)) a.tr.push(round_time(a, a.g), ((uint64_t)a.g << 32) | m, rp, rs, rt, GSIM_TRACE_RECV_RPC, 1);
+            if (up && a.tr.on(rp)) a.tr.push(round_time(a, a.g), ((uint64_t)a.g << 32) | m, rp, rs, rt, GSIM_TRACE_RECV_RPC, 1);
         }
+        if (!up) continue;
         listed_copy(a, r, m, owner, par, claim_hi, tpa, n_acc, n_gray, n_first, s_new2, true);
     }
     n_acc = wave_sum_u64(n_acc);
@@ -3930,6 +3954,7 @@ static int ihave_walk(gsim_handle* h, IhaveStage* st)
     hipLaunchKernelGGL(k_promise_insert, dim3(std::min<int64_t>((h->e + 255) / 256, 16384)), dim3(256), 0, h->stream,
                        d->d_pcand, d->d_prom, d->prom_ticks, a.prom_idx, h->e);
     d->resp_round = a.g + 2;
+    d->resp_marked = false;
     return hip_check(h, hipGetLastError(), "k_ihave");
 }
 
@@ -4215,6 +4240,11 @@ int deliver_round_prepare(gsim_handle* h, int64_t round)
     Deliver* d = h->dl;
     if (!d) { h->err = "gsim_msgs_init not called"; return GSIM_ESTATE; }
     if (round < 0 || round >= 0x7FFFFFFF) { h->err = "round out of range [0, 2^31-1)"; return GSIM_ERANGE; }
+    if (d->lat_on && round + GSIM_MAX_VDELAY >= 0x7FFFFFFF) {
+        // a copy arriving now completes at round + vdelay, which its cell must hold
+        h->err = "round out of range: with validation latencies rounds end at 2^31 - 2 - GSIM_MAX_VDELAY";
+        return GSIM_ERANGE;
+    }
     if (d->next_round >= 0 && round != d->next_round) {
         h->err = "rounds must be consecutive";
         return GSIM_ESTATE;
@@ -4322,14 +4352,27 @@ int deliver_round_send(gsim_handle* h, int64_t round)
 // Copies arriving in round g at this handle's peers, one entry per copy:
 // the receiver's record of the sender | slot << 32 (the IWANT responses).
 // *d_n entries, at most cap.
-int deliver_round_queue(gsim_handle* h, int64_t round, const uint64_t* q, const uint32_t* d_n, int64_t cap)
+int deliver_round_queue(gsim_handle* h, int64_t round, const uint64_t* q, const uint32_t* d_n, int64_t cap,
+                        bool lost_check)
 {
     Deliver* d = h->dl;
     RoundArgs a = make_round_args(h, round);
     const size_t lds2 = (size_t)nnew_words(d) * 4;
     hipLaunchKernelGGL(k_gossip_deliver, dim3(2048), dim3(256), lds2, h->stream, a, q, d_n,
-                       (const uint32_t*)h->d_owner, cap);
+                       (const uint32_t*)h->d_owner, cap, lost_check ? 1 : 0);
     return hip_check(h, hipGetLastError(), "k_gossip_deliver");
+}
+
+// Connections are about to change (churn, the PX connector): answers still
+// queued keep the state of their connections as it is now.
+int deliver_connections_change(gsim_handle* h)
+{
+    Deliver* d = h->dl;
+    if (!d || d->resp_round < 0 || d->resp_marked) return GSIM_OK;
+    hipLaunchKernelGGL(k_resp_mark, dim3(1024), dim3(256), 0, h->stream, d->d_resp, (const uint32_t*)d->d_nresp,
+                       d->resp_cap, (const uint32_t*)h->d_rev, (const uint8_t*)h->d_rstate);
+    d->resp_marked = true;
+    return hip_check(h, hipGetLastError(), "k_resp_mark");
 }
 
 // ---- copy push as bitmaps -------------------------------
@@ -4582,8 +4625,9 @@ int deliver_round_post(gsim_handle* h, int64_t round)
     if (d->resp_round == round) {
         // the messages handleIWant sent in control round 1 arrive with this round's copies
         ProfScope ps(h, GSIM_K_GOSSIP);
-        rc = deliver_round_queue(h, round, d->d_resp, d->d_nresp, d->resp_cap);
+        rc = deliver_round_queue(h, round, d->d_resp, d->d_nresp, d->resp_cap, d->resp_marked);
         d->resp_round = -1;
+        d->resp_marked = false;
         if (rc) return rc;
     }
     if (!lazy_commits(h)) rc = deliver_flush(h);
@@ -5144,6 +5188,12 @@ int gsim_msgs_init(gsim_handle* h, const gsim_msg_config* cfg)
         h->err = "too many edges or peers for the seen-set claim encoding (< 2^30 - 1)";
         return GSIM_ERANGE;
     }
+    // promises live IWantFollowupTime: the promise ring holds one index per heartbeat of that span
+    if ((cfg->heartbeat_ns / (cfg->rounds + 1) + h->gp.iwant_followup_time_ns) / cfg->heartbeat_ns + 2 > kMaxPromTicks) {
+        h->err = "heartbeat_ns too short for IWantFollowupTime: (heartbeat_ns / (rounds + 1) + IWantFollowupTime) / "
+                 "heartbeat_ns + 2 must not exceed 64 promise ticks";
+        return GSIM_EINVAL;
+    }
     if (cfg->topic_slots < 0 || (cfg->topic_slots > 0 && (int64_t)cfg->ring != cfg->topic_slots * std::max(1, h->t))) {
         h->err = "topic_slots: every topic owns topic_slots ring slots, so ring must be n_topics * topic_slots";
         return GSIM_EINVAL;
@@ -5240,7 +5290,7 @@ int gsim_msgs_init(gsim_handle* h, const gsim_msg_config* cfg)
     {
         const int64_t hb = cfg->heartbeat_ns;
         const int64_t span = hb / (cfg->rounds + 1) + h->gp.iwant_followup_time_ns;
-        d->prom_ticks = (int32_t)std::min<int64_t>(span / hb + 2, 64);
+        d->prom_ticks = (int32_t)(span / hb + 2);            // (<= kMaxPromTicks: checked above)
         d->prom_made.assign((size_t)d->prom_ticks, -1);
     }
     d->resp_cap = cfg->max_arrivals > 0 ? cfg->max_arrivals : std::max<int64_t>(8 * h->n, 1 << 20);
@@ -5350,6 +5400,12 @@ static int publish_impl(gsim_handle* h, const gsim_msg* msgs, int32_t count, int
             return GSIM_EINVAL;
         }
         if (msgs[m].vdelay > GSIM_MAX_VDELAY) { h->err = "vdelay above GSIM_MAX_VDELAY"; return GSIM_EINVAL; }
+        // (once a latency was published gsim_round refuses those rounds: so does every publication)
+        if (round + ((msgs[m].vdelay || d->lat_on) ? GSIM_MAX_VDELAY : 0) >= 0x7FFFFFFF) {
+            h->err = "publication round out of range [0, 2^31-1) (a message with vdelay > 0, or any message once one "
+                     "was published: [0, 2^31-1-GSIM_MAX_VDELAY))";
+            return GSIM_ERANGE;
+        }
         if (msgs[m].vdelay && h->gt) {
             h->err = "a validation latency (vdelay) cannot be combined with the peer gater";
             return GSIM_ESTATE;
@@ -5528,6 +5584,18 @@ int gsim_step(gsim_handle* h, uint64_t tick, int32_t n_ticks, const gsim_msg* ms
         for (int64_t q = 0; q < nr; ++q)
             if (round_off[q + 1] < round_off[q] || round_off[q + 1] - round_off[q] > INT32_MAX) return GSIM_EINVAL;
         nmsg = round_off[nr];
+    }
+    {
+        // every round of the call must be one gsim_round accepts: nothing runs otherwise
+        bool lat = d->lat_on;
+        for (int64_t q = 0; q < nmsg && !lat; ++q) lat = msgs[q].vdelay != 0;
+        const int64_t last = 0x7FFFFFFE - (lat ? GSIM_MAX_VDELAY : 0);
+        if (tick > (uint64_t)(last / R) || (int64_t)tick + n_ticks > last / R + 1 ||
+            ((int64_t)tick + n_ticks) * R - 1 > last) {
+            h->err = lat ? "gsim_step: rounds out of range (with validation latencies they end at 2^31 - 2 - GSIM_MAX_VDELAY)"
+                         : "gsim_step: rounds out of range [0, 2^31-1)";
+            return GSIM_ERANGE;
+        }
     }
     int rc = deliver_check_errors(h);                // what the last call left
     if (rc) return rc;

@@ -806,7 +806,9 @@ void scoretracer_release(gsim_handle* h);   // scoretracer.hip
 // exchanges between them, shard.hip)
 int deliver_round_prepare(gsim_handle* h, int64_t round);
 int deliver_round_send(gsim_handle* h, int64_t round);
-int deliver_round_queue(gsim_handle* h, int64_t round, const uint64_t* q, const uint32_t* d_n, int64_t cap);
+int deliver_round_queue(gsim_handle* h, int64_t round, const uint64_t* q, const uint32_t* d_n, int64_t cap,
+                        bool lost_check);
+int deliver_connections_change(gsim_handle* h);    // before connections go up or down: queued answers note theirs
 int deliver_round_post(gsim_handle* h, int64_t round);
 int deliver_round_control(gsim_handle* h, int64_t round);
 int deliver_round_ihave(gsim_handle* h, int64_t round);

@@ -3085,6 +3085,10 @@ int gsim_read_snapshot(gsim_handle* h, int64_t obs_lo, int64_t obs_hi, gsim_peer
 // edges[2q + d] = the edge of direction d of connection q (n2 = 2 * count).
 static int apply_connections(gsim_handle* h, const uint32_t* d_edges, int32_t n2, int32_t up, int64_t now)
 {
+    {
+        const int rcq = deliver_connections_change(h);   // IWANT answers under way
+        if (rcq) return rcq;
+    }
     const int grid = (n2 + 255) / 256;
     HbArgs a = make_hb_args(h, 0, now, 0);   // ctl_in/ctl_out cover both inbox planes
     ChurnArgs c{};

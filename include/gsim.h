@@ -284,7 +284,30 @@ int gsim_px_connect(gsim_handle* h, int64_t now_ns, uint32_t* pairs, int64_t cap
  * round, 0xFFFFFFFF = unseen): the timecache (timecache/first_seen_cache.go)
  * restricted to messages that can still arrive.  Publishing into a slot ends
  * the propagation of its previous message; SeenMsgTTL and the ring must
- * outlast a message's propagation (they do for every reference configuration). */
+ * outlast a message's propagation (they do for every reference configuration).
+ *
+ * Bounds of the clock (each checked on the host, before anything runs):
+ *   rounds        >= 2 (GSIM_EINVAL from gsim_msgs_init).
+ *   heartbeat_ns  > 0, and long enough for the promise ring: IWANT promises
+ *                 are kept per heartbeat for IWantFollowupTime, so
+ *                   (heartbeat_ns / (rounds + 1) + IWantFollowupTime) / heartbeat_ns + 2
+ *                 (the promise ticks, integer division) must not exceed 64
+ *                 (GSIM_EINVAL from gsim_msgs_init; with the default
+ *                 IWantFollowupTime of 3 s and two rounds a tick: 48 ms at the least).
+ *   round number  0 .. 2^31 - 2: a seen-set cell holds a first-seen round in 31
+ *                 bits and 2^31 - 1 is not a round.  gsim_round and gsim_publish
+ *                 of any other round, and a gsim_step whose last round would
+ *                 pass it, return GSIM_ERANGE and change nothing.
+ *   vdelay        0 .. GSIM_MAX_VDELAY (GSIM_EINVAL from gsim_publish).  A copy
+ *                 arriving in round g completes in round g + vdelay, which its
+ *                 cell must hold: a message with vdelay > 0 is refused
+ *                 (GSIM_ERANGE) in a round above 2^31 - 2 - GSIM_MAX_VDELAY, and
+ *                 once one was published gsim_round, gsim_step and gsim_publish
+ *                 (of any message) refuse those rounds too.
+ *   slot reuse    a slot may be republished reuse_guard = (max(HistoryLength,
+ *                 HistoryGossip) + promise ticks + 2) * rounds rounds after its
+ *                 message's last first delivery, not earlier (GSIM_ESTATE from
+ *                 the next call that checks the error flags). */
 /* Subscription changes between ticks (Topic.Subscribe / Cancel through
  * pubsub.go:1051-1079 announcements and the router's Join / Leave,
  * gossipsub.go:1047-1124), for (peer, topic) pairs.  join = 1: Join(topic):
@@ -356,7 +379,8 @@ typedef struct gsim_msg_config {
     int32_t ring;            /* message slots (live-message window), 1..8192 */
     int32_t rounds;          /* propagation rounds per heartbeat, >= 2 */
     int64_t t0_ns;           /* virtual time of tick 0 */
-    int64_t heartbeat_ns;    /* heartbeat interval (GossipSubParams.HeartbeatInterval) */
+    int64_t heartbeat_ns;    /* heartbeat interval (GossipSubParams.HeartbeatInterval), > 0; its lower
+                                bound: "Bounds of the clock" above */
     int64_t max_frontier;    /* 0: default.  > 0: a memory bound on the round lists of member-compacted
                                 layouts (topic_slots > 0): the claim list holds this many entries
                                 (default max(4 N, 2^20)), each forwarder list half as many; a round

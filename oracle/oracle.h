@@ -227,9 +227,14 @@ enum {
     ORC_EV_PX_PEER = 19,     /* a: pruner, b: a peer of the PRUNE's PX list, topic,
                                 mid: the pruned peer, g: its rank in the list (makePrune) */
     ORC_EV_RPC_MSG = 20,     /* a: sender, b: receiver, mid, topic, g: the round it arrives in,
-                                x: 0 a forwarded copy (sent in g), 1 an IWANT answer (sent in g - 1) */
+                                x: 0 a forwarded copy (sent in g), 1 an IWANT answer (sent in g - 1),
+                                3 an IWANT answer sent in g - 1 and lost: its connection went down
+                                before round g (never received) */
     ORC_EV_RPC_IWANT = 21,   /* a: requester, b: advertiser, mid, topic, g: the round the IWANT is sent
                                 in (handleIHave's reply, gossipsub.go:611-627); it arrives in g + 1 */
+    ORC_EV_VALIDATE = 22,    /* a: receiver, b: sender, mid, topic, g: the round the first copy arrives in
+                                (markSeen; the validation is pending), x: the round its verdict lands in
+                                (g + vdelay, where ORC_EV_SEEN with x = 1 follows) */
 };
 typedef struct orc_event { int32_t kind, topic; uint32_t a, b; int64_t g; uint64_t mid; int64_t x; } orc_event;
 void    orc_msgs_log(orc_msgs* m, int32_t on);

@@ -317,6 +317,7 @@ static void handle_copy(orc_net* s, orc_msgs* m, priv* p, int64_t g, int64_t now
         /* markSeen + ValidateMessage (promises fulfilled); the verdict
          * lands vdelay rounds later (complete_validations) */
         *cell = (uint32_t)(g + vdelay);
+        orc_log(m, ORC_EV_VALIDATE, i, s->col[er], slot, t, g, g + vdelay);
         stats[1]++;
         orc_gossip_fulfill(m, i, slot);
         if (p->slot_last) p->slot_last[slot] = g;
@@ -395,9 +396,13 @@ void orc_round(orc_net* s, orc_msgs* m, int64_t g)
     p->nfp = 0;
     /* IWANT responses sent in the previous round arrive with them */
     for (int64_t q = 0; q < p->ngr; ++q) {
+        /* a connection that was up when the answer was sent and went down since
+         * (churn between two ticks): the copy is lost with its stream, sent and
+         * never received (x = 3 in the log) */
+        const int up = !((p->gr[q].resp & 2) && !(s->estate[p->gr[q].er] & GSIM_ES_CONNECTED));
         orc_log(m, ORC_EV_RPC_MSG, s->col[p->gr[q].er], p->gr[q].recv, p->gr[q].slot, (int32_t)m->topic[p->gr[q].slot],
-                g, 1);
-        ar_push(p, p->gr[q].recv, p->gr[q].slot, p->gr[q].er, 1);
+                g, up ? 1 : 3);
+        if (up) ar_push(p, p->gr[q].recv, p->gr[q].slot, p->gr[q].er, 1);
     }
     p->ngr = 0;
 

@@ -404,7 +404,8 @@ void orc_gossip_iwant(orc_net* s, orc_msgs* m, int64_t g)
         p->gr[p->ngr].recv = s->col[ei];
         p->gr[p->ngr].slot = slot;
         p->gr[p->ngr].er = er;
-        p->gr[p->ngr].resp = 1;
+        /* (bit 1: the requester's connection to i is up as the answer is sent) */
+        p->gr[p->ngr].resp = (uint8_t)(1 | ((s->estate[er] & GSIM_ES_CONNECTED) ? 2 : 0));
         p->ngr++;
     }
     p->niw = 0;

@@ -9,7 +9,7 @@ import oracle_binding as ob
 from gsim import _abi
 from gsim.params import Second
 from test_delivery import R, T0
-from test_heartbeat import SEED, assert_same, tick_time
+from test_heartbeat import SEED, assert_same
 
 
 def restrict_to_subscriptions(st, net):
@@ -38,11 +38,13 @@ def oracle_trace(ev, msgs, lo, hi):
         mid, topic = int(e["mid"]), int(e["topic"])
         if kind == ob.EV_RPC_MSG:
             # a message RPC: SEND_RPC at the sender, RECV_RPC at the receiver; an IWANT
-            # answer (x = 1) is sent the round before it arrives
+            # answer (x = 1) is sent the round before it arrives (x = 3: and lost with its
+            # connection, which went down in between: never received)
             g, x = int(e["g"]), int(e["x"])
+            lost, x = x == 3, x & 1
             if lo <= a < hi:
                 out.append((msgs.round_time(g - x), mid, a, b, topic, _abi.TRACE_SEND_RPC, x))
-            if lo <= b < hi:
+            if lo <= b < hi and not lost:
                 out.append((msgs.round_time(g), mid, b, a, topic, _abi.TRACE_RECV_RPC, x))
             continue
         if kind == ob.EV_RPC_IWANT:
@@ -84,7 +86,7 @@ def oracle_trace(ev, msgs, lo, hi):
 def run_parity(net, params, th, gp, st, ticks, sched, ring=256, behaviour=None, churn=None, after_tick=None,
                eng=None, after_heartbeat=None, px_log=None, trace=None, trace_log=None, topic_slots=0, gater=None,
                gater_log=None, subs=None, local_only=False, trace_every_round=False,
-               max_frontier=0, step=False):
+               max_frontier=0, step=False, rounds=R, hb=Second, t0=T0):
     """Run `ticks` on a fresh engine loaded with `st`'s state and on the
     oracle; assert identical state, seen-set and totals after every tick.
     churn: {tick: [(pairs, up), ...]} applied just before the tick.
@@ -109,7 +111,12 @@ def run_parity(net, params, th, gp, st, ticks, sched, ring=256, behaviour=None, 
     bound of member-compacted layouts: small values force their overflow
     fallbacks).  trace_every_round: the engine's trace is read after every round (events
     stamped after the last round run stay for a later read, resolved once)
-    and the tick's reads together must equal the oracle's log."""
+    and the tick's reads together must equal the oracle's log.
+    rounds, hb, t0: the message clock (gsim_msg_config.rounds, heartbeat_ns,
+    t0_ns) of both sides: tick k is at t0 + k * hb and owns the rounds
+    k * rounds ... k * rounds + rounds - 1 (`sched` is keyed by those).
+    step=N (an int > 1): `ticks` run N at a time, one gsim_step call each,
+    compared after every call (no churn, hooks or PX inside a call)."""
     from gsim.engine import Engine
     pushed = eng is None
     if eng is None:
@@ -121,8 +128,8 @@ def run_parity(net, params, th, gp, st, ticks, sched, ring=256, behaviour=None, 
             st.push_to_engine(eng)
         if topic_slots:
             ring = st.T * topic_slots
-        eng.msgs_init(ring, R, T0, Second, topic_slots=topic_slots, max_frontier=max_frontier)
-        msgs = ob.Msgs(net.n, st.T, ring, R, T0, Second, behaviour=behaviour, topic_slots=topic_slots)
+        eng.msgs_init(ring, rounds, t0, hb, topic_slots=topic_slots, max_frontier=max_frontier)
+        msgs = ob.Msgs(net.n, st.T, ring, rounds, t0, hb, behaviour=behaviour, topic_slots=topic_slots)
         if trace is not None:
             eng.trace_config(trace[0], trace[1], 1 << 22)
             msgs.log()
@@ -132,17 +139,27 @@ def run_parity(net, params, th, gp, st, ticks, sched, ring=256, behaviour=None, 
             eng.set_peer_gater(gater)
             st.enable_gater(gater)
         lib = ob.load()
-        for kk in ticks:
-            now = tick_time(kk)
-            parts = []
+        ticks = list(ticks)
+        nstep = int(step) if step is not True and step is not False and int(step) > 1 else 1
+        parts = []
+        for idx, kk in enumerate(ticks):
+            now = t0 + kk * hb
+            # step=N: the engine runs the ticks of a call together, at the first of them
+            call = ticks[idx:idx + nstep] if idx % nstep == 0 else None
+            last = idx % nstep == nstep - 1 or idx == len(ticks) - 1
+            if nstep > 1:
+                assert not (churn or {}).get(kk) and not (subs or {}).get(kk) or call, "churn inside a gsim_step call"
+                assert call is None or call == list(range(kk, kk + len(call))), "a gsim_step call runs consecutive ticks"
             for (pairs, up) in (churn or {}).get(kk, []):
-                st.churn(pairs, up=up, now=now - Second // 2)
-                eng.set_connections(pairs, up=up, now=now - Second // 2)
+                st.churn(pairs, up=up, now=now - hb // 2)
+                eng.set_connections(pairs, up=up, now=now - hb // 2)
             for (pairs, join) in (subs or {}).get(kk, []):
-                st.set_subscriptions(pairs, join, kk, now - Second // 2, SEED)
-                eng.set_subscriptions(pairs, join, kk, now - Second // 2)
+                st.set_subscriptions(pairs, join, kk, now - hb // 2, SEED)
+                eng.set_subscriptions(pairs, join, kk, now - hb // 2)
             if step:
-                eng.step(kk, 1, {g: sched[g] for g in range(kk * R, kk * R + R) if g in sched})
+                if call:
+                    eng.step(kk, len(call), {g: sched[g] for g in range(kk * rounds, (kk + len(call)) * rounds)
+                                             if g in sched})
             else:
                 eng.refresh_scores(now)
                 eng.heartbeat(kk, now)
@@ -156,7 +173,7 @@ def run_parity(net, params, th, gp, st, ticks, sched, ring=256, behaviour=None, 
             msgs.heartbeat(st, kk, now, SEED)
             if after_heartbeat:
                 after_heartbeat(kk, eng, st, msgs)
-            for g in range(kk * R, kk * R + R):
+            for g in range(kk * rounds, kk * rounds + rounds):
                 for msg in sched.get(g, []):
                     mid, t, o, inv = msg[:4]
                     msgs.publish(st, mid, t, o, inv, g, vdelay=msg[4] if len(msg) > 4 else 0)
@@ -167,6 +184,8 @@ def run_parity(net, params, th, gp, st, ticks, sched, ring=256, behaviour=None, 
                     eng.round(g)
                 if trace is not None and trace_every_round:
                     parts.append(eng.trace_read())
+            if not last:
+                continue
             assert eng.msg_stats() == msgs.stats, f"totals differ at tick {kk}: {eng.msg_stats()} vs {msgs.stats}"
             seen = eng.read(_abi.F_SEEN, into=msgs.seen.copy()) if local_only else eng.read(_abi.F_SEEN)
             lput = eng.read(_abi.F_LASTPUT, into=msgs.lastput.copy()) if local_only else eng.read(_abi.F_LASTPUT)
@@ -179,6 +198,7 @@ def run_parity(net, params, th, gp, st, ticks, sched, ring=256, behaviour=None, 
                 got, want = eng.trace_read(), oracle_trace(msgs.events(), msgs, trace[0], trace[1])
                 if parts:
                     got = np.concatenate(parts + [got])
+                    parts = []
                     got = got[np.lexsort((got["msg_id"], got["topic"], got["reason"], got["other"], got["type"],
                                           got["peer"], got["timestamp"]))]
                 assert len(got) == len(want), f"trace length differs at tick {kk}: {len(got)} vs {len(want)}"
@@ -202,7 +222,7 @@ def run_parity(net, params, th, gp, st, ticks, sched, ring=256, behaviour=None, 
                 if gater_log is not None:
                     gater_log.append(st.gater_throttled())
             if gp.PeerExchange:
-                t_px = now + Second // 2
+                t_px = now + hb // 2
                 got, want = eng.px_connect(t_px), st.px_connect(t_px)
                 assert np.array_equal(got, want), f"PX connections differ after tick {kk}: {len(got)} vs {len(want)}"
                 if px_log is not None:
@@ -214,13 +234,14 @@ def run_parity(net, params, th, gp, st, ticks, sched, ring=256, behaviour=None, 
         eng.close()
 
 
-def subscribed_schedule(rng, ticks, net, T, rate, inv_frac, member_only=True, verdicts=None, vdelays=None):
+def subscribed_schedule(rng, ticks, net, T, rate, inv_frac, member_only=True, verdicts=None, vdelays=None, rounds=R):
     """Poisson(rate) publications per topic per tick at uniform rounds; the
     origin is a uniform member of the topic (or any peer).  The verdict is
     reject with probability inv_frac, or drawn from `verdicts` (probabilities
     of accept / reject / ignore / throttle / signature) when given.  vdelays:
     validation latencies (rounds) drawn uniformly per message, as a fifth
-    tuple element (gsim_msg.vdelay)."""
+    tuple element (gsim_msg.vdelay).  rounds: the rounds of a tick."""
+    R = rounds
     sched, mid = {}, 0
     members = [np.nonzero((net.sub >> np.uint64(t)) & np.uint64(1))[0] for t in range(T)]
     for k in ticks:
