@@ -4068,6 +4068,12 @@ bool deliver_report_view(gsim_handle* h, ReportView* v)
     return true;
 }
 
+int64_t deliver_next_round(gsim_handle* h)
+{
+    const Deliver* d = h->dl;
+    return d && d->next_round > 0 ? d->next_round : 0;
+}
+
 int64_t deliver_last_round_time(gsim_handle* h)
 {
     const Deliver* d = h->dl;
@@ -5410,6 +5416,10 @@ static int publish_impl(gsim_handle* h, const gsim_msg* msgs, int32_t count, int
             h->err = "a validation latency (vdelay) cannot be combined with the peer gater";
             return GSIM_ESTATE;
         }
+        if (msgs[m].vdelay && h->ct) {
+            h->err = "a validation latency (vdelay) cannot be combined with connection tags (near-first credit is not built)";
+            return GSIM_ESTATE;
+        }
         if (msgs[m].vdelay && h->sh && !h->sh->push) {
             h->err = "a validation latency (vdelay) on shards needs the copy push (GSIM_SHARD_PULL unset)";
             return GSIM_ERANGE;
@@ -5474,6 +5484,12 @@ static int publish_impl(gsim_handle* h, const gsim_msg* msgs, int32_t count, int
         // the last round's claims are committed before slots are reset (k_reset_slots)
         const int rcf = deliver_flush(h);
         if (rcf) return rcf;
+    }
+    if (h->ct) {
+        // connection tags: a caller that ran a reuse guard's rounds without a fold point gets one before a slot can go
+        const int64_t guard = (int64_t)(std::max(h->gp.history_gossip, h->gp.history_length) + d->prom_ticks + 2) * d->cfg.rounds;
+        const int rct = conntags_publish(h, round, guard);
+        if (rct) return rct;
     }
     if (!d_src) {
         e = hipMemcpyAsync(d->d_pub, msgs, sizeof(gsim_msg) * (size_t)count, hipMemcpyHostToDevice, h->stream);
@@ -5589,6 +5605,13 @@ int gsim_step(gsim_handle* h, uint64_t tick, int32_t n_ticks, const gsim_msg* ms
         // every round of the call must be one gsim_round accepts: nothing runs otherwise
         bool lat = d->lat_on;
         for (int64_t q = 0; q < nmsg && !lat; ++q) lat = msgs[q].vdelay != 0;
+        if (h->ct)
+            for (int64_t q = 0; q < nmsg; ++q)
+                if (msgs[q].vdelay) {
+                    h->err = "gsim_step: a validation latency (vdelay) cannot be combined with connection tags "
+                             "(near-first credit is not built)";
+                    return GSIM_ESTATE;
+                }
         const int64_t last = 0x7FFFFFFE - (lat ? GSIM_MAX_VDELAY : 0);
         if (tick > (uint64_t)(last / R) || (int64_t)tick + n_ticks > last / R + 1 ||
             ((int64_t)tick + n_ticks) * R - 1 > last) {

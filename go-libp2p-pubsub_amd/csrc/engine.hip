@@ -1031,6 +1031,7 @@ int ensure_slots(gsim_handle* h, const uint64_t* need)
     if (!rc) rc = relayout_one(h, &h->d_backoff, 1, d0, d1, S0, S1);
     if (!rc) rc = relayout_one(h, extra_ctl_slot(h), 2, d0, d1, S0, S1);
     if (!rc) rc = relayout_one(h, deliver_gsel_slot(h), 1, d0, d1, S0, S1);
+    if (!rc) rc = conntags_relayout(h, d0, d1, S0, S1);
     if (rc) { (void)hipFree(d1); return rc; }
     (void)hipFree(h->d_smask);
     h->d_smask = d1;
@@ -1294,6 +1295,7 @@ int gsim_destroy(gsim_handle* h)
     free_deliver(h);
     trace_release(h);
     scoretracer_release(h);
+    conntags_release(h);
     report_release(h);
     peerreport_release(h);
     scorereport_release(h);
@@ -1362,6 +1364,7 @@ int gsim_load_graph(gsim_handle* h, int64_t n, const uint32_t* row_ptr, const ui
     free_deliver(h);
     trace_release(h);
     scoretracer_release(h);
+    conntags_release(h);
     h->n = n;
     h->e = E;
     h->n_ips = n_ips;
@@ -1597,6 +1600,11 @@ int gsim_refresh_scores(gsim_handle* h, int64_t now)
 {
     GSIM_ENTER(h);
     GSIM_NEED_GRAPH(h);
+    // connection tags (conntags.hip): the last tick's first deliveries, then the decay instants
+    if (h->ct) {
+        const int rc = conntags_refresh(h, now);
+        if (rc) return rc;
+    }
     return launch_refresh_scores(h, now);
 }
 

@@ -468,6 +468,7 @@ struct ScoreReport; // the score report's device scratch and what-if tables (sco
 struct MeshPaths;   // the mesh path report's per-peer words and counters (meshpaths.hip)
 struct RelayReport; // the relay report's device scratch (relayreport.hip)
 struct ScoreTracer; // the score tracer's delivery records and batch scratch (scoretracer.hip)
+struct ConnTags;    // connection tags: the delivery tag planes, since[] and the trim's scratch (conntags.hip)
 using MsgReport = struct ::gsim_msg_report;   // (the call gsim_msg_report hides the struct's name in C++)
 
 // The peer gater's device state as the delivery kernels see it (gater.hip;
@@ -612,6 +613,7 @@ struct gsim_handle {
     gsim::MeshPaths* mp = nullptr;   // gsim_mesh_paths scratch (meshpaths.hip), allocated at the first call; a new graph drops it
     gsim::RelayReport* rl = nullptr; // gsim_relay_report scratch (relayreport.hip), allocated at the first call
     gsim::ScoreTracer* st = nullptr; // gsim_score_tracer_config (scoretracer.hip); a new graph drops it
+    gsim::ConnTags* ct = nullptr;    // gsim_conn_tags_config (conntags.hip), nullptr: off; a new graph drops it
 
     // owned peers / observer rows (all of them unless sharded)
     int64_t olo() const { return sh ? sh->own_lo : 0; }
@@ -802,6 +804,18 @@ int relay_finish(gsim_handle* h, struct gsim_relay_row* peers, uint64_t* cto, st
 int64_t deliver_last_round_time(gsim_handle* h);   // time of the last round run (INT64_MAX: none yet)
 void trace_release(gsim_handle* h);   // trace.hip
 void scoretracer_release(gsim_handle* h);   // scoretracer.hip
+// conntags.hip: the connection tags (gsim_conn_tags_config).  Every hook returns at once while h->ct is null.
+void conntags_release(gsim_handle* h);
+int conntags_fold(gsim_handle* h);                       // commits the pending claims, then the bumps of the rounds since the last fold
+int conntags_refresh(gsim_handle* h, int64_t now);       // the fold, then the decay instants `now` has reached
+// before a publication in `round` resets slots: the fold, if the last one lies `guard` rounds (the slots' reuse guard) back
+int conntags_publish(gsim_handle* h, int64_t round, int64_t guard);
+// connections going down or up (edges[2q + d]: both directions, device memory): the fold, then their tags dropped and, going up, since = now
+int conntags_connections(gsim_handle* h, const uint32_t* d_edges, int32_t n2, int32_t up, int64_t now);
+int conntags_leave(gsim_handle* h, const uint32_t* d_pairs, int32_t count);   // Leave of (peer, topic) pairs (device memory): those rows' planes cleared
+// ensure_slots: the [S0][E] tag planes re-laid out into S1 planes (device masks m0 -> m1), before h->S changes
+int conntags_relayout(gsim_handle* h, const uint64_t* m0, const uint64_t* m1, int32_t S0, int32_t S1);
+int64_t deliver_next_round(gsim_handle* h);              // deliver.hip: the first round not yet run (0: none was)
 // round stages (deliver.hip; gsim_round runs them in order, a sharded group
 // exchanges between them, shard.hip)
 int deliver_round_prepare(gsim_handle* h, int64_t round);

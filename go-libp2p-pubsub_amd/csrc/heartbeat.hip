@@ -3089,6 +3089,10 @@ static int apply_connections(gsim_handle* h, const uint32_t* d_edges, int32_t n2
         const int rcq = deliver_connections_change(h);   // IWANT answers under way
         if (rcq) return rcq;
     }
+    if (h->ct) {                                         // connection tags: dropped at both ends, since = now going up
+        const int rct = conntags_connections(h, d_edges, n2, up, now);
+        if (rct) return rct;
+    }
     const int grid = (n2 + 255) / 256;
     HbArgs a = make_hb_args(h, 0, now, 0);   // ctl_in/ctl_out cover both inbox planes
     ChurnArgs c{};
@@ -3196,6 +3200,7 @@ int gsim_set_subscriptions(gsim_handle* h, const uint32_t* pairs, int32_t count,
         }
     }
     int rc = deliver_flush(h);
+    if (!rc && h->ct) rc = conntags_fold(h); // the deliveries before the Join / Leave bump the tags first
     if (!rc) rc = materialize_mcnt(h);       // stats_prune reads meshMessageDeliveries
     if (!rc && !need.empty()) rc = ensure_slots(h, need.data());
     if (rc) return rc;
@@ -3258,6 +3263,10 @@ int gsim_set_subscriptions(gsim_handle* h, const uint32_t* pairs, int32_t count,
     if (e != hipSuccess) return hip_check(h, e, "k_subscribe");
     h->mesh_version++;            // router mesh / fanout bits changed: delivery masks rebuild
     h->score_version++;
+    if (!join && h->ct) {         // removeDeliveryTag: the leaving routers' tags of the topic
+        const int rct = conntags_leave(h, (const uint32_t*)h->d_churn, count);
+        if (rct) return rct;
+    }
     if (!join) {
         h->unjoined_zero = false; // a peer that left keeps records of the topic
         h->all_joined = false;

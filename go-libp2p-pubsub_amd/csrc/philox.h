@@ -57,6 +57,7 @@ enum Purpose : uint32_t {
     P_GATER = 16,      // the peer gater's rand.Float64()      peer_gater.go:357
     P_JOIN = 17,       // Join's getPeers                     gossipsub.go:1068-1092
     P_PX_LEAVE = 18,   // makePrune's getPeers (Leave's PRUNE) gossipsub.go:1118, 1866-1906
+    P_TRIM = 19,       // the connection manager's order among equal values (gsim_conn_trim; topic 0, item = neighbour id)
 };
 
 // Key of a choice made per (observer, other peer, message slot): the other

@@ -127,6 +127,16 @@ class CMsgConfig(Structure):
                 ("max_frontier", c_int64), ("max_arrivals", c_int64), ("topic_slots", c_int64)]
 
 
+class CConnTagParams(Structure):
+    """struct gsim_conn_tag_params (32 bytes): the tag tracer's delivery tags (tag_tracer.go:13-31)."""
+    _fields_ = [("bump", c_int32), ("cap", c_int32), ("decay_amount", c_int32), ("_pad", c_int32),
+                ("decay_interval_ns", c_int64), ("t0_ns", c_int64)]
+
+
+CONN_CONNECTED, CONN_PROTECTED, CONN_GRACE = 0x01, 0x02, 0x04   # gsim_conn_values flags
+P_TRIM = 19                                                     # the trim's selection purpose (philox.h)
+
+
 class CMsg(Structure):
     _fields_ = [("id", c_uint64), ("topic", c_uint32), ("origin", c_uint32), ("verdict", ctypes.c_uint8),
                 ("vdelay", ctypes.c_uint8), ("_pad", ctypes.c_uint8 * 6)]
@@ -453,6 +463,12 @@ SIGNATURES = [
     ("gsim_gossip_stats", c_int32, [c_void_p, c_void_p]),
     ("gsim_set_connections", c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int64]),
     ("gsim_px_connect", c_int32, [c_void_p, c_int64, c_void_p, c_int64, c_void_p]),
+    ("gsim_default_conn_tag_params", c_int32, [c_int64, POINTER(CConnTagParams)]),
+    ("gsim_conn_tags_config", c_int32, [c_void_p, POINTER(CConnTagParams)]),
+    ("gsim_conn_tags_read", c_int32, [c_void_p, c_int32, c_void_p]),
+    ("gsim_conn_values", c_int32, [c_void_p, c_int64, c_int64, c_void_p, c_void_p]),
+    ("gsim_conn_trim", c_int32, [c_void_p, c_uint64, c_int64, c_int32, c_int32, c_int64, c_void_p, c_int64,
+                                 POINTER(c_int64)]),
     ("gsim_trace_config", c_int32, [c_void_p, c_uint32, c_uint32, c_int64]),
     ("gsim_trace_read", c_int32, [c_void_p, c_void_p, c_int64, c_void_p]),
     ("gsim_score_tracer_config", c_int32, [c_void_p, c_int64, c_int64, c_int64]),

@@ -389,6 +389,53 @@ class Engine:
         self._check(self.lib.gsim_px_connect(self.h, int(now), _ptr(out), int(cap), ctypes.byref(n)))
         return out[:min(n.value, cap)].copy()
 
+    # -- connection tags and the connection manager's trim (gsim.connmgr reads the results) --
+    def conn_tags_config(self, bump: int = 1, cap: int = 15, decay_amount: int = 1,
+                         decay_interval: Optional[int] = None, t0: Optional[int] = None, off: bool = False):
+        """The tag tracer's decaying delivery tags on every router (gsim_conn_tags_config;
+        tag_tracer.go): the defaults are GossipSubConnTag*, decay_interval in ns (10 min),
+        t0 the phase of the decay instants (the message clock's t0).  After msgs_init.
+        Calling it again starts from zero tags; off=True frees them."""
+        if off:
+            self._check(self.lib.gsim_conn_tags_config(self.h, None))
+            return
+        c = _abi.CConnTagParams()
+        self.lib.gsim_default_conn_tag_params(int(self._msg_cfg.t0_ns if t0 is None else t0), ctypes.byref(c))
+        c.bump, c.cap, c.decay_amount = int(bump), int(cap), int(decay_amount)
+        if decay_interval is not None:
+            c.decay_interval_ns = int(decay_interval)
+        self._check(self.lib.gsim_conn_tags_config(self.h, ctypes.byref(c)))
+
+    def conn_tags(self, topic: int) -> np.ndarray:
+        """The delivery tags of `topic` per connection, u8 [E] in edge order (gsim_conn_tags_read)."""
+        out = np.zeros(self.net.e, dtype=np.uint8)
+        self._check(self.lib.gsim_conn_tags_read(self.h, int(topic), _ptr(out)))
+        return out
+
+    def conn_values(self, now: int, grace: int = 0):
+        """(value i32 [E], flags u8 [E]) per connection in edge order: the sum of its
+        delivery tags and _abi.CONN_CONNECTED | CONN_PROTECTED | CONN_GRACE (gsim_conn_values)."""
+        value = np.zeros(self.net.e, dtype=np.int32)
+        flags = np.zeros(self.net.e, dtype=np.uint8)
+        self._check(self.lib.gsim_conn_values(self.h, int(now), int(grace), _ptr(value), _ptr(flags)))
+        return value, flags
+
+    def conn_trim(self, tick: int, now: int, low: int, high: int, grace: int = 0, count_only: bool = False):
+        """The connection manager's trim on every router at once (gsim_conn_trim): the
+        connections closed, as sorted unique (a < b) pairs [n, 2]; they went down as
+        through set_connections(pairs, up=False, now).  high = 0 forces the trim of
+        every router above low.  count_only: their number, nothing closes."""
+        n = ctypes.c_int64(0)
+        if count_only:
+            self._check(self.lib.gsim_conn_trim(self.h, int(tick), int(now), int(low), int(high), int(grace), None, 0,
+                                                ctypes.byref(n)))
+            return n.value
+        cap = max(1, self.net.e // 2)
+        out = np.empty((cap, 2), dtype=np.uint32)             # (untouched beyond the rows the call writes)
+        self._check(self.lib.gsim_conn_trim(self.h, int(tick), int(now), int(low), int(high), int(grace), _ptr(out),
+                                            int(cap), ctypes.byref(n)))
+        return out[:n.value].copy()
+
     # gsim_trace_event
     TRACE_DTYPE = np.dtype([("timestamp", np.int64), ("msg_id", np.uint64), ("peer", np.uint32),
                             ("other", np.uint32), ("topic", np.int32), ("type", np.uint8), ("reason", np.uint8),

@@ -276,6 +276,86 @@ int gsim_set_connections(gsim_handle* h, const uint32_t* pairs, int32_t count, i
  * pairs connected, sorted.  Single engines only. */
 int gsim_px_connect(gsim_handle* h, int64_t now_ns, uint32_t* pairs, int64_t cap, int64_t* n_connected);
 
+/* ---- connection tags and the connection manager's trim -- */
+/* The tag tracer (tag_tracer.go) and the observable of go-libp2p's
+ * BasicConnMgr that gossipsub_connmgr_test.go pins, for every router at once.
+ * Per router i and connection e = (i, j):
+ *   protected(e)  direct[e], or j in i's mesh of any topic (tagPeerIfDirect,
+ *                 tagMeshPeer / untagMeshPeer: Protect / Unprotect by tag
+ *                 name).  Derived from the router state, not stored.
+ *   dtag[t][e]    u8, for every topic t that i has joined: DeliverMessage of an
+ *                 ACCEPTED first delivery of a message of t whose ReceivedFrom
+ *                 is j does v = min(v + bump, cap) (BumpSumBounded(0, cap)).
+ *                 The origin's own cell bumps nothing; the verdicts reject /
+ *                 ignore / throttle / bad signature bump nothing; a first
+ *                 delivery pulled by IWANT bumps the advertiser.
+ *   decay         DecayFixed(decay_amount) at the instants t0 + k * interval,
+ *                 k >= 1: v = max(0, v - amount), applied by the first
+ *                 gsim_refresh_scores(now) with now >= that instant, after
+ *                 the bumps of everything delivered before that refresh; a
+ *                 refresh that crosses several instants decrements as often.
+ *   Leave         removes the router's tags of the topic (removeDeliveryTag);
+ *                 a later Join starts at 0.
+ *   down / up     a connection going down drops its tags at both ends; one
+ *                 coming up (churn, PX) starts at 0 with since[e] = now (the
+ *                 connection manager's firstSeen, for the grace period).
+ *                 Connections present at gsim_conn_tags_config are out of grace.
+ *   value(e)      the sum of dtag[t][e] over the router's joined topics.
+ * Declared differences: the decayer's Resolution is the heartbeat; every
+ * (router, topic) shares the phase t0 (a tag's own registration time is not
+ * modelled); near-first credit (nearFirst, peers delivering while the first
+ * copy validates) is not built: while tags are configured a publication with
+ * vdelay > 0 is refused with GSIM_ESTATE (gsim_publish, gsim_step: nothing is
+ * published).  The bumps are folded from the committed seen-set cells (first
+ * sender, first-seen round) once per refresh and at the start of every call
+ * below and of gsim_set_connections, gsim_px_connect, gsim_set_subscriptions.
+ * A caller that runs rounds without any of these for as long as a ring slot
+ * must rest before it is reused ((max(HistoryLength, HistoryGossip) + the
+ * promise ticks + 2) * rounds) gets a fold at its next publication, before a
+ * slot can be reset: no first delivery is lost between two folds.  An engine that never configures tags allocates and launches nothing.
+ * Single engines only: every call returns GSIM_ESTATE on a shard of a group
+ * and, but for the config, before gsim_conn_tags_config. */
+typedef struct gsim_conn_tag_params {
+    int32_t bump, cap, decay_amount;  /* GossipSubConnTagBumpMessageDelivery 1, ...MessageDeliveryCap 15, ...DecayAmount 1 */
+    int32_t _pad;
+    int64_t decay_interval_ns;        /* GossipSubConnTagDecayInterval, 10 min */
+    int64_t t0_ns;                    /* phase of the decay instants */
+} gsim_conn_tag_params;
+/* The reference's values (tag_tracer.go:13-31) with phase t0_ns. */
+int gsim_default_conn_tag_params(int64_t t0_ns, gsim_conn_tag_params* out);
+/* After gsim_msgs_init (else GSIM_ESTATE), and refused with GSIM_ESTATE once a
+ * message with vdelay > 0 was published on the handle (copies may be pending
+ * validation; a later gsim_msgs_init starts over).  GSIM_EINVAL unless cap in 1..255,
+ * bump >= 1, decay_amount >= 1, decay_interval_ns > 0.  Every tag starts at 0
+ * and the first deliveries counted are those of the rounds not yet run.
+ * Calling it again starts from zero tags; NULL turns the tags off and frees
+ * their memory (u8 [S][E] topic slot planes and i64 [E]); so does a new graph. */
+int gsim_conn_tags_config(gsim_handle* h, const gsim_conn_tag_params* p);
+/* out[E], edge order: dtag[topic][e] (0 where the router has not joined). */
+int gsim_conn_tags_read(gsim_handle* h, int32_t topic, uint8_t* out);
+#define GSIM_CONN_CONNECTED 0x01
+#define GSIM_CONN_PROTECTED 0x02
+#define GSIM_CONN_GRACE     0x04   /* since + grace_ns > now_ns */
+/* value[E] and flags[E] (GSIM_CONN_*), edge order; either may be NULL (both:
+ * the pending bumps are folded and nothing is read). */
+int gsim_conn_values(gsim_handle* h, int64_t now_ns, int64_t grace_ns, int32_t* value, uint8_t* flags);
+/* TrimOpenConns / getConnsToClose restated, for every router at once on the
+ * state before any close.  A router with connected > high trims (high == 0:
+ * every router with connected > low, the forced trim).  Its candidates are its
+ * connections that are connected, not protected and out of grace (since +
+ * grace_ns <= now_ns), ordered ascending by (value, key), the key being
+ * Philox(seed; tick, router, topic 0, purpose 19, neighbour id) above the row
+ * position (the selection keys of DESIGN.md §3.4); it closes the first
+ * connected - low of them, all of them if there are fewer.  The union over
+ * the routers, as unique pairs (a < b) sorted ascending, is written to pairs
+ * (*n of them) and applied as gsim_set_connections(pairs, *n, up = 0, now_ns):
+ * a connection either end chose closes, so a router may end below low.
+ * pairs NULL or cap 0: *n is counted and nothing closes; 0 < cap < *n:
+ * GSIM_ERANGE, nothing closes.  GSIM_EINVAL unless 0 <= low, 0 <= high,
+ * grace_ns >= 0 and (high == 0 or low <= high). */
+int gsim_conn_trim(gsim_handle* h, uint64_t tick, int64_t now_ns, int32_t low, int32_t high, int64_t grace_ns,
+                   uint32_t* pairs, int64_t cap, int64_t* n);
+
 /* ---- message propagation ------------------------------ */
 /* Rounds are numbered globally: round g belongs to heartbeat tick g / rounds
  * and happens at virtual time
