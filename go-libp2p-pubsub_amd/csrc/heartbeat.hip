@@ -3189,7 +3189,8 @@ int gsim_set_subscriptions(gsim_handle* h, const uint32_t* pairs, int32_t count,
     const int32_t T = std::max(1, h->t);
     std::vector<uint64_t> need;
     for (int32_t q = 0; q < count; ++q) {
-        if ((int64_t)pairs[2 * q] >= h->n || (int32_t)pairs[2 * q + 1] >= T) {
+        // (compared unsigned: a topic of 2^31 or more is no negative number)
+        if ((int64_t)pairs[2 * q] >= h->n || pairs[2 * q + 1] >= (uint32_t)T) {
             h->err = "subscription pair out of range";
             return GSIM_EINVAL;
         }

@@ -1688,7 +1688,14 @@ int gsim_group_msgs_init(gsim_group* g, const gsim_msg_config* cfg)
         // message it first saw in the round before (grown on demand);
         // max_frontier sets the initial size
         s->fcap = cfg->max_frontier > 0 ? cfg->max_frontier : std::max<int64_t>(8 * (s->own_hi - s->own_lo), 1 << 16);
-        s->ccap = std::max<int64_t>(4 * gmax, 1 << 14);
+        // GRAFT/PRUNE records of one exchange to one shard: at most one per (topic, cross edge
+        // into it).  That bound itself while it stays under 2^22 records (32 MiB a shard pair): a
+        // dense start at T = 64 prunes in every topic at once, and four records a ghost peer
+        // overflowed on 1500 peers; above it the larger of the two (an overflow fails the call).
+        int64_t xmax_c = 0;
+        for (int q = 0; q < K; ++q) xmax_c = std::max<int64_t>(xmax_c, s->xoff[(size_t)q + 1] - s->xoff[(size_t)q]);
+        s->ccap = std::max<int64_t>(std::max<int64_t>(4 * gmax, 1 << 14),
+                                    std::min<int64_t>(xmax_c * (int64_t)std::max(1, h->t), (int64_t)1 << 22));
         const int64_t ncross = s->xoff[(size_t)K];
         rc = GSIM_OK;
         auto A = [&](auto** p, size_t n) { if (!rc) rc = dalloc(h, p, n); };

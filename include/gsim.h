@@ -401,7 +401,12 @@ int gsim_conn_trim(gsim_handle* h, uint64_t tick, int64_t now_ns, int32_t low, i
  * tick's refresh, as gsim_set_connections); the GRAFT/PRUNE are handled with
  * the heartbeat's in control round 0.  Peers that withdrew a topic drop its
  * messages (pubsub.go:1094-1098).  Leave's PRUNEs carry no peer exchange.
- * JOIN / LEAVE / GRAFT / PRUNE trace events.  Single engine. */
+ * JOIN / LEAVE / GRAFT / PRUNE trace events.  Single engine.
+ * A pair whose peer is not below n or whose topic is not below n_topics (as
+ * unsigned numbers: 0xFFFFFFFF is no topic) fails the whole call with
+ * GSIM_EINVAL before anything changes; so does gsim_load_graph for a
+ * subscription bit at or beyond n_topics, and gsim_create takes at most 64
+ * topics (GSIM_ERANGE). */
 int gsim_set_subscriptions(gsim_handle* h, const uint32_t* pairs, int32_t count, int32_t join, uint64_t tick,
                            int64_t now_ns);
 
