@@ -2193,7 +2193,8 @@ constexpr int kIhBatch = GSIM_IH_BATCH;   // MM walks: slots whose cells one lan
 constexpr uint32_t kIhHub = GSIM_IH_HUB;
 constexpr int kIhSlices = GSIM_IH_SLICES;
 #ifdef GSIM_DIAG_IH
-// diagnostic build (counts and wave clocks only, results unchanged), per LP (1, 2):
+// diagnostic build (counts and wave clocks only, results unchanged), per LP (1, 2; the
+// slot loop of the instances that are not member-major fills the entries of LP 1):
 // [0] push row walks, [1] push edges, [2] their gossip targets, [3] pull row walks,
 // [4] pull edges, [5] their gossiping advertisers, [6] push clocks, [7] pull clocks
 // (per wave), read by gsim_diag_ih_counts
@@ -2202,15 +2203,62 @@ __device__ unsigned long long g_ih_diag[16];
 #else
 #define IH_D(...)
 #endif
+// Flat push walk of the slot loop (the instances that are not member-major):
+// every holder of a push slot whose row has at most 64 connections reads its
+// own emitGossip choices once, as a bit mask by row position, and the wave's
+// (holder, target) pairs are laid out one per lane.  0: every
+// holder walks its row with its lane group, as before.
+#ifndef GSIM_IH_FLAT
+#define GSIM_IH_FLAT 1
+#endif
+// waves per SIMD the slot-loop instances are fitted to: 1 leaves the compiler free (112
+// VGPRs, 4 waves at C3's instance); 5 spills 14 VGPRs and costs 0.25 ms of gossip per tick
+// at C3, 6 spills 276 and costs 3.6 ms (profiles/ihave_flat_ab.txt)
+#ifndef GSIM_IH_WPE_DENSE
+#define GSIM_IH_WPE_DENSE 1
+#endif
+constexpr bool kIhFlat = GSIM_IH_FLAT != 0;
+constexpr uint32_t kIhFlatRow = 64;   // longest row a mask covers
+constexpr int kIhFlatTab = 256;       // per-wave LDS table of pairs (holder lane << 8 | row position)
+constexpr size_t kIhFlatLds = kIhFlat ? 4 * kIhFlatTab * sizeof(uint16_t) : 0;
+
+// The non-zero bytes of the 8 at s (any alignment), as bits 0..7.
+__device__ __forceinline__ uint64_t nz_bytes8(const uint8_t* s)
+{
+    uint64_t w;
+    __builtin_memcpy(&w, s, 8);
+    const uint64_t k7 = 0x7F7F7F7F7F7F7F7Full;
+    const uint64_t nz = ((((w & k7) + k7) | w) & ~k7) >> 7;   // 1 in every non-zero byte
+    return (nz * 0x0102040810204080ull) >> 56;
+}
+// Bit q: s[q] != 0, for the deg <= 64 bytes at s.  Reads nothing outside them:
+// whole 8-byte words from s, the row's last 8 bytes for the remainder (the
+// overlap sets the same bits again), single bytes in a row shorter than 8.
+__device__ __forceinline__ uint64_t row_sel_mask(const uint8_t* s, uint32_t deg)
+{
+    uint64_t m = 0;
+#pragma unroll
+    for (uint32_t j = 0; j < kIhFlatRow / 8; ++j)
+        if (8 * j + 8 <= deg) m |= nz_bytes8(s + 8 * j) << (8 * j);
+    if (deg >= 8) {
+        if (deg & 7u) m |= nz_bytes8(s + deg - 8) << (deg - 8);
+    } else {
+        for (uint32_t q = 0; q < deg; ++q) m |= (uint64_t)(s[q] != 0) << q;
+    }
+    return m;
+}
+
 template <int W, bool LAT, bool SP, bool MM = false, int LP = 0>
-__global__ __launch_bounds__(256, MM ? GSIM_IH_WPE : 1) void k_ihave(IhArgs a_, const uint32_t* gcount)
+__global__ __launch_bounds__(256, MM ? GSIM_IH_WPE : GSIM_IH_WPE_DENSE) void k_ihave(IhArgs a_, const uint32_t* gcount)
 {
     const IhArgs& a = a_;
-    extern __shared__ uint16_t s_act[];   // [ring] candidate slots (bit 15: push), then response staging
+    extern __shared__ uint16_t s_act[];   // [ring] candidate slots (bit 15: push), then response staging,
+                                          // then (slot loop) the flat push walk's pair tables
     __shared__ int s_n;
     if (a.nresp[3] & 4u) return;          // a truncation may apply: k_ihave_pairs
     const int wid = threadIdx.x >> 6;
     uint64_t* stage = reinterpret_cast<uint64_t*>(s_act + ((a.ring + 3) & ~3)) + wid * kRespStage;
+    uint16_t* ftab = reinterpret_cast<uint16_t*>(stage + (4 - wid) * kRespStage) + wid * kIhFlatTab;
     // LP 2: the listed wave (its block and wave) and the slice
     const uint32_t hw = LP == 2 ? a.hubw[blockIdx.x / kIhSlices] : 0u;
     const uint32_t bx = LP == 2 ? (hw & 0x07FFFFFFu) >> 2 : blockIdx.x;
@@ -2274,6 +2322,9 @@ __global__ __launch_bounds__(256, MM ? GSIM_IH_WPE : 1) void k_ihave(IhArgs a_, 
         }
         nstage = 0;
     };
+    IH_D(unsigned long long d_pw = 0, d_pe = 0, d_ph = 0, d_qw = 0, d_qe = 0, d_qh = 0, d_pc = 0, d_qc = 0;)
+    // flat push walk: Philox keys use global ids (each lane's own, shuffled to its pairs)
+    const uint32_t own_g = !MM && kIhFlat && a.gid && vp ? a.gid[pl] : (uint32_t)pl;
     // MM: the member-major phases below walk a row once for many slots
     for (int k0 = 0; !MM && k0 < nact; k0 += kSlotBatch) {
         uint64_t cv[kSlotBatch];
@@ -2304,6 +2355,18 @@ __global__ __launch_bounds__(256, MM ? GSIM_IH_WPE : 1) void k_ihave(IhArgs a_, 
             const uint64_t mask = __ballot(me);
             if (!mask) continue;
             const int64_t cb_m = (int64_t)a.cs.cbase[m];
+            IH_D(const unsigned long long c_s0 = clock64();)
+            // an edge's outcome (wave-uniform call): counted, and a response staged for the queue
+            auto emit = [&](bool req, bool resp, uint32_t r) {
+                n_req += req;
+                n_resp += resp;
+                const uint64_t sb = __ballot(resp);
+                if (sb) {
+                    if (nstage + __popcll(sb) > kRespStage) flush_stage();
+                    if (resp) stage[nstage + __popcll(sb & ((1ull << lane) - 1))] = (uint64_t)r | ((uint64_t)m << 32);
+                    nstage += __popcll(sb);
+                }
+            };
             // one chunk of a row walk: lane gl of a group of `gw` lanes takes
             // edge beg + off + gl of peer me_id's row (me_pl: its plane of t)
             auto chunk = [&](uint32_t off, uint32_t gl_, uint32_t beg, uint32_t deg, uint32_t me_id, uint32_t me_g,
@@ -2312,9 +2375,11 @@ __global__ __launch_bounds__(256, MM ? GSIM_IH_WPE : 1) void k_ihave(IhArgs a_, 
                 const uint32_t e = beg + off + gl_;
                 bool req = false, resp = false;
                 uint32_t r = 0;
+                IH_D(if (push) d_pe += v; else d_qe += v;)
                 if (push) {
                     // holder me_id walks its row: the peers it gossiped t to
                     if (v && me_pl >= 0 && a.gsel[me_pl + e]) {
+                        IH_D(d_ph++;)
                         const uint32_t p = a.col[e], re = a.rev[e];
                         // p's gate on i, p has not seen m (a shard: p one of its receivers)
                         const int64_t pci = a.cs.at(cb_m, t, p);
@@ -2335,6 +2400,7 @@ __global__ __launch_bounds__(256, MM ? GSIM_IH_WPE : 1) void k_ihave(IhArgs a_, 
                         const uint32_t i = a.col[e];
                         const uint64_t mi = smask_of(a.smask, i);        // i's emitGossip choices: its row
                         if (slot_has(mi, t) && a.gsel[slot_idx(mi, t, a.E, re)] && a.gstate[e]) {
+                            IH_D(d_qh++;)
                             const int64_t ici = a.cs.at(cb_m, t, i);
                             req = holds_in_window(ici >= 0 ? a.cs.cell[ici] : kUnseen64, a.g, a.lo_round, tick_round, inv,
                                                   i == origin, LAT ? a.mlat[m] : 0u);
@@ -2350,20 +2416,85 @@ __global__ __launch_bounds__(256, MM ? GSIM_IH_WPE : 1) void k_ihave(IhArgs a_, 
                         }
                     }
                 }
-                n_req += req;
-                n_resp += resp;
-                const uint64_t sb = __ballot(resp);
-                if (sb) {
-                    if (nstage + __popcll(sb) > kRespStage) flush_stage();
-                    if (resp) stage[nstage + __popcll(sb & ((1ull << lane) - 1))] = (uint64_t)r | ((uint64_t)m << 32);
-                    nstage += __popcll(sb);
-                }
+                emit(req, resp, r);
             };
+            // Flat push walk.  Each holder lane with a row of at most kIhFlatRow
+            // connections forms the mask of its targets from its own gsel bytes
+            // (its plane of t; no plane or no target: 0).  A wave scan of the
+            // popcounts numbers the wave's (holder, target) pairs; they pass
+            // through the wave's LDS table, a window of kIhFlatTab at a time,
+            // and each batch of 64 runs the push body of `chunk`, one lane per
+            // pair: the same triples, keys, responses and counts as the group
+            // walk.  Holders with longer rows keep the walks below.
+            uint64_t flat = 0;
+            if (kIhFlat && push) {
+                const uint32_t dl = rp1 - rp0;
+                const bool fl = me && dl <= kIhFlatRow;
+                flat = __ballot(fl);
+                if (flat) {
+                    uint64_t tm = 0;
+                    if (fl && dl) {
+                        const uint64_t om = smask_of(a.smask, (uint32_t)pl);
+                        if (slot_has(om, t)) tm = row_sel_mask(a.gsel + slot_idx(om, t, a.E, rp0), dl);
+                    }
+                    n_walk += fl;
+                    IH_D(d_pw += fl; d_pe += fl ? dl : 0u; d_ph += (unsigned)__popcll(tm);)
+                    const uint32_t cnt = (uint32_t)__popcll(tm);
+                    uint32_t inc = cnt;                       // inclusive scan over the lanes
+#pragma unroll
+                    for (int o = 1; o < 64; o <<= 1) {
+                        const uint32_t up = (uint32_t)__shfl_up((int)inc, o, 64);
+                        if (lane >= o) inc += up;
+                    }
+                    const uint32_t total = (uint32_t)__shfl((int)inc, 63, 64);
+                    uint32_t ni = inc - cnt;                  // this lane's next pair
+                    for (uint32_t w0 = 0; w0 < total; w0 += kIhFlatTab) {
+                        const uint32_t wn = total - w0 < (uint32_t)kIhFlatTab ? total - w0 : (uint32_t)kIhFlatTab;
+                        while (tm && ni < w0 + wn) {          // (ni >= w0: earlier pairs went to earlier windows)
+                            ftab[ni - w0] = (uint16_t)((lane << 8) | __builtin_ctzll(tm));
+                            tm &= tm - 1;
+                            ++ni;
+                        }
+                        __builtin_amdgcn_wave_barrier();
+                        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+                        for (uint32_t q0 = 0; q0 < wn; q0 += 64) {
+                            const bool v = q0 + lane < wn;
+                            const uint32_t pr = v ? ftab[q0 + lane] : (uint32_t)lane << 8;
+                            const int hl = (int)(pr >> 8);
+                            const uint32_t e = (uint32_t)__shfl((int)rp0, hl, 64) + (pr & 0xFFu);
+                            const bool ign_s = __shfl((int)ign_l, hl, 64) != 0;
+                            const uint32_t me_g = (uint32_t)__shfl((int)own_g, hl, 64);
+                            const uint32_t me_id = (uint32_t)(p0 + hl);
+                            bool req = false, resp = false;
+                            if (v) {
+                                // the edge, then the target's gate and cell: independent loads together
+                                const uint32_t p = a.col[e], re = a.rev[e];
+                                const uint8_t ge = a.gstate[e];
+                                const bool own = p >= a.rlo && p < a.rhi;     // (a shard: one of its receivers)
+                                const int64_t pci = own ? a.cs.at(cb_m, t, p) : -1;
+                                const uint8_t gr = own ? a.gstate[re] : (uint8_t)0;
+                                const uint64_t pc = pci >= 0 ? a.cs.cell[pci] : 0ull;
+                                req = gr && pci >= 0 && pc == kUnseen64;
+                                if (req) {
+                                    if (a.tr.ev) trace_iwant(a, p, me_id, m);
+                                    const uint64_t key = pair_key(a.seed, (uint32_t)a.tick, a.gid ? a.gid[p] : p, 0,
+                                                                  P_PROMISE, m, me_g);
+                                    atomicMin(reinterpret_cast<unsigned long long*>(&a.pcand[re]), (unsigned long long)key);
+                                    resp = a.respond && ge && !ign_s && peertx_allows(a, m, e, me_id);
+                                }
+                            }
+                            emit(req, resp, e);
+                        }
+                        __builtin_amdgcn_wave_barrier();      // the window's reads, before the next one's writes
+                        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+                    }
+                }
+            }
             // rows longer than 4 groups' width are walked by the whole wave
             // afterwards, so one hub does not hold its wave's other groups
             // through its chunks
-            const uint64_t longm = mask & long_lanes;
-            uint64_t gm = mask & ~longm & gmask;
+            const uint64_t longm = mask & long_lanes & ~flat;
+            uint64_t gm = mask & ~longm & ~flat & gmask;
             while (__ballot(gm != 0)) {
                 int bs = -1;
                 if (gm) { bs = __ffsll((long long)gm) - 1; gm &= gm - 1; }
@@ -2375,6 +2506,7 @@ __global__ __launch_bounds__(256, MM ? GSIM_IH_WPE : 1) void k_ihave(IhArgs a_, 
                 const uint64_t me_m = smask_of(a.smask, me_id);
                 const int64_t me_pl = slot_has(me_m, t) ? slot_idx(me_m, t, a.E, 0) : -1;
                 n_walk += (gl == 0 && bs >= 0);
+                IH_D(if (push) d_pw += (gl == 0 && bs >= 0); else d_qw += (gl == 0 && bs >= 0);)
                 // rows longer than the group are walked in W-edge chunks (wave-uniform trip count)
                 const uint32_t deg = bs >= 0 ? end - beg : 0u;
                 for (uint32_t off = 0; __ballot(off < deg) != 0; off += W)
@@ -2389,12 +2521,13 @@ __global__ __launch_bounds__(256, MM ? GSIM_IH_WPE : 1) void k_ihave(IhArgs a_, 
                 const uint64_t me_m = smask_of(a.smask, me_id);
                 const int64_t me_pl = slot_has(me_m, t) ? slot_idx(me_m, t, a.E, 0) : -1;
                 n_walk += (lane == 0);
+                IH_D(if (push) d_pw += (lane == 0); else d_qw += (lane == 0);)
                 for (uint32_t off = 0; off < end - beg; off += 64)
                     chunk(off, (uint32_t)lane, beg, end - beg, me_id, me_g, ign_s, me_pl);
             }
+            IH_D(if (push) d_pc += clock64() - c_s0; else d_qc += clock64() - c_s0;)
         }
     }
-    IH_D(unsigned long long d_pw = 0, d_pe = 0, d_ph = 0, d_qw = 0, d_qe = 0, d_qh = 0, d_pc = 0, d_qc = 0;)
     if constexpr (MM) {
         IH_D(const unsigned long long c_p0 = clock64();)
         // the member's held / unseen window slots (k_gossip_count_mm), else its cells below
@@ -2688,7 +2821,7 @@ __global__ __launch_bounds__(256, MM ? GSIM_IH_WPE : 1) void k_ihave(IhArgs a_, 
     }
     flush_stage();
 #ifdef GSIM_DIAG_IH
-    if (MM && LP) {
+    if (!MM || LP) {      // (the slot loop's instances: the lp1 entries)
         unsigned long long* dg = g_ih_diag + (LP == 2 ? 8 : 0);
         const unsigned long long v6[6] = {wave_sum_u64(d_pw), wave_sum_u64(d_pe), wave_sum_u64(d_ph),
                                           wave_sum_u64(d_qw), wave_sum_u64(d_qe), wave_sum_u64(d_qh)};
@@ -3914,12 +4047,16 @@ static void launch_ihave_w(gsim_handle* h, IhaveStage* st, const IhArgs& a)
             hipLaunchKernelGGL((k_ihave<W, true, true, true>), dim3(grid), dim3(256), st->lds, h->stream, a, gc);
         else
             hipLaunchKernelGGL((k_ihave<W, false, true, true>), dim3(grid), dim3(256), st->lds, h->stream, a, gc);
-    } else if (a.mlat)
-        hipLaunchKernelGGL((k_ihave<W, true, true>), dim3(st->grid), dim3(256), st->lds, h->stream, a, (const uint32_t*)h->dl->d_gcount);
+        return;
+    }
+    // the slot loop: its waves' pair tables follow the response staging
+    const size_t lds = st->lds + kIhFlatLds;
+    if (a.mlat)
+        hipLaunchKernelGGL((k_ihave<W, true, true>), dim3(st->grid), dim3(256), lds, h->stream, a, (const uint32_t*)h->dl->d_gcount);
     else if (sparse_layout(h))
-        hipLaunchKernelGGL((k_ihave<W, false, true>), dim3(st->grid), dim3(256), st->lds, h->stream, a, (const uint32_t*)h->dl->d_gcount);
+        hipLaunchKernelGGL((k_ihave<W, false, true>), dim3(st->grid), dim3(256), lds, h->stream, a, (const uint32_t*)h->dl->d_gcount);
     else
-        hipLaunchKernelGGL((k_ihave<W, false, false>), dim3(st->grid), dim3(256), st->lds, h->stream, a, (const uint32_t*)h->dl->d_gcount);
+        hipLaunchKernelGGL((k_ihave<W, false, false>), dim3(st->grid), dim3(256), lds, h->stream, a, (const uint32_t*)h->dl->d_gcount);
 }
 
 static int ihave_walk(gsim_handle* h, IhaveStage* st)
