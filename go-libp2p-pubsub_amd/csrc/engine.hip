@@ -1295,6 +1295,7 @@ int gsim_destroy(gsim_handle* h)
     free_deliver(h);
     trace_release(h);
     scoretracer_release(h);
+    routerstate_release(h);
     conntags_release(h);
     report_release(h);
     peerreport_release(h);
@@ -1364,6 +1365,7 @@ int gsim_load_graph(gsim_handle* h, int64_t n, const uint32_t* row_ptr, const ui
     free_deliver(h);
     trace_release(h);
     scoretracer_release(h);
+    routerstate_release(h);
     conntags_release(h);
     h->n = n;
     h->e = E;

@@ -469,6 +469,7 @@ struct MeshPaths;   // the mesh path report's per-peer words and counters (meshp
 struct RelayReport; // the relay report's device scratch (relayreport.hip)
 struct ScoreTracer; // the score tracer's delivery records and batch scratch (scoretracer.hip)
 struct ConnTags;    // connection tags: the delivery tag planes, since[] and the trim's scratch (conntags.hip)
+struct RouterState; // the seen cache and the IWANT promises of externally driven routers (routerstate.hip)
 using MsgReport = struct ::gsim_msg_report;   // (the call gsim_msg_report hides the struct's name in C++)
 
 // The peer gater's device state as the delivery kernels see it (gater.hip;
@@ -614,6 +615,7 @@ struct gsim_handle {
     gsim::RelayReport* rl = nullptr; // gsim_relay_report scratch (relayreport.hip), allocated at the first call
     gsim::ScoreTracer* st = nullptr; // gsim_score_tracer_config (scoretracer.hip); a new graph drops it
     gsim::ConnTags* ct = nullptr;    // gsim_conn_tags_config (conntags.hip), nullptr: off; a new graph drops it
+    gsim::RouterState* rs = nullptr; // gsim_router_state_config (routerstate.hip); a new graph drops it
 
     // owned peers / observer rows (all of them unless sharded)
     int64_t olo() const { return sh ? sh->own_lo : 0; }
@@ -804,6 +806,7 @@ int relay_finish(gsim_handle* h, struct gsim_relay_row* peers, uint64_t* cto, st
 int64_t deliver_last_round_time(gsim_handle* h);   // time of the last round run (INT64_MAX: none yet)
 void trace_release(gsim_handle* h);   // trace.hip
 void scoretracer_release(gsim_handle* h);   // scoretracer.hip
+void routerstate_release(gsim_handle* h);   // routerstate.hip
 // conntags.hip: the connection tags (gsim_conn_tags_config).  Every hook returns at once while h->ct is null.
 void conntags_release(gsim_handle* h);
 int conntags_fold(gsim_handle* h);                       // commits the pending claims, then the bumps of the rounds since the last fold

@@ -5,7 +5,7 @@ Host-side mirror of the reference's plugin surface for the hot path:
 ``GossipSubParams`` (score_params.go, gossipsub.go) and an ``Engine`` that
 drives libgsim.so's HIP kernels through the C ABI in include/gsim.h.
 """
-from . import _abi, tracer
+from . import _abi, routerstate, tracer
 from .engine import Engine, GsimError, Network, random_regular
 from .params import (DefaultDecayInterval, DefaultDecayToZero, DefaultGossipSubParams, DefaultPeerGaterParams,
                      GossipSubParams, Hour, Microsecond, Millisecond, Minute, Nanosecond, NewPeerGaterParams,
@@ -17,5 +17,5 @@ __all__ = [
     "PeerScoreThresholds", "GossipSubParams", "DefaultGossipSubParams", "ScoreParameterDecay",
     "ScoreParameterDecayWithBase", "Nanosecond", "Microsecond", "Millisecond", "Second", "Minute", "Hour",
     "DefaultDecayInterval", "DefaultDecayToZero", "TimeCacheDuration", "PeerGaterParams", "NewPeerGaterParams",
-    "DefaultPeerGaterParams", "_abi", "tracer",
+    "DefaultPeerGaterParams", "_abi", "routerstate", "tracer",
 ]

@@ -121,6 +121,27 @@ SCORE_EVENT_DTYPE = [("mid", "<u8"), ("now_ns", "<i8"), ("observer", "<u4"), ("p
                      ("topic", "u1"), ("kind", "u1"), ("_pad", "u1", (4,))]
 
 
+# gsim_router_event (include/gsim.h): the seen cache's and the gossip tracer's calls
+RS_SEEN_ADD, RS_SEEN_HAS, RS_PROMISE, RS_FULFILL = range(4)
+
+
+class CRouterEvent(Structure):
+    """struct gsim_router_event (32 bytes): one seen-cache or gossip-tracer call on one observer."""
+    _fields_ = [("mid", c_uint64), ("now_ns", c_int64), ("observer", c_uint32), ("peer", c_uint32),
+                ("kind", c_uint8), ("_pad", c_uint8 * 7)]
+
+
+class CBrokenRow(Structure):
+    """struct gsim_broken_row (16 bytes): the broken promises of one (observer, peer)."""
+    _fields_ = [("observer", c_uint32), ("peer", c_uint32), ("count", c_uint32), ("_pad", c_uint32)]
+
+
+# numpy views of gsim_router_event and gsim_broken_row
+ROUTER_EVENT_DTYPE = [("mid", "<u8"), ("now_ns", "<i8"), ("observer", "<u4"), ("peer", "<u4"), ("kind", "u1"),
+                      ("_pad", "u1", (7,))]
+BROKEN_ROW_DTYPE = [("observer", "<u4"), ("peer", "<u4"), ("count", "<u4"), ("_pad", "<u4")]
+
+
 # (name, restype, argtypes) for every symbol include/gsim.h declares.
 class CMsgConfig(Structure):
     _fields_ = [("ring", c_int32), ("rounds", c_int32), ("t0_ns", c_int64), ("heartbeat_ns", c_int64),
@@ -318,7 +339,8 @@ TOPIC_SNAPSHOT_DTYPE = [("time_in_mesh_ns", "<i8"), ("first_message_deliveries",
                         ("mesh_message_deliveries", "<f8"), ("invalid_message_deliveries", "<f8")]
 
 KERNEL_CLASSES = ["refresh_score", "score", "ip_colocation", "heartbeat", "control", "publish", "send",
-                  "commit", "accept", "gossip", "churn", "tracer_sort", "tracer_resolve", "tracer_apply"]
+                  "commit", "accept", "gossip", "churn", "tracer_sort", "tracer_resolve", "tracer_apply",
+                  "router_sort", "router_resolve", "router_apply", "router_sweep", "router_broken"]
 BEHAVE_IGNORE_IWANT = 0x01
 
 # gsim_host_transport callbacks (include/gsim.h)
@@ -476,6 +498,12 @@ SIGNATURES = [
     ("gsim_score_tracer_gc", c_int32, [c_void_p, c_int64]),
     ("gsim_score_tracer_stats", c_int32, [c_void_p, c_void_p]),
     ("gsim_score_tracer_settled", c_int32, [c_void_p, c_void_p]),
+    ("gsim_router_state_config", c_int32, [c_void_p, c_int64, c_int64, c_int32, c_int64, c_int64]),
+    ("gsim_router_state_events", c_int32, [c_void_p, c_void_p, c_int64, c_void_p]),
+    ("gsim_router_state_sweep", c_int32, [c_void_p, c_int64]),
+    ("gsim_router_state_throttle", c_int32, [c_void_p, c_void_p, c_int64, c_void_p]),
+    ("gsim_router_state_broken", c_int32, [c_void_p, c_int64, c_int32, c_void_p, c_int64, c_void_p]),
+    ("gsim_router_state_stats", c_int32, [c_void_p, c_void_p]),
     ("gsim_set_direct_peers", c_int32, [c_void_p, c_void_p]),
     ("gsim_profile", c_int32, [c_void_p, c_int32]),
     ("gsim_profile_read", c_int32, [c_void_p, c_void_p, c_void_p, c_int32]),

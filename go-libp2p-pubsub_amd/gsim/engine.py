@@ -489,6 +489,67 @@ class Engine:
         self._check(self.lib.gsim_score_tracer_settled(self.h, _ptr(out)))
         return int(out[0]), bool(out[1])
 
+    # -- router state: seen cache and IWANT promises (gsim.routerstate builds the arrays) --
+    def router_state_config(self, seen_cap: int, promises_cap: int, strategy: int = 0, seen_ttl: int = 0,
+                            followup: int = 0):
+        """Size the seen cache (seen_cap entries) and the gossip tracer's
+        promises (promises_cap), over all observers.  strategy 0: first-seen,
+        1: last-seen; seen_ttl 0: TimeCacheDuration; followup 0: the engine's
+        IWantFollowupTime (gsim_router_state_config).  Calling it again drops
+        everything."""
+        self._check(self.lib.gsim_router_state_config(self.h, int(seen_cap), int(promises_cap), int(strategy),
+                                                      int(seen_ttl), int(followup)))
+
+    def router_state_events(self, events: np.ndarray) -> np.ndarray:
+        """Apply a batch of seen-cache and gossip-tracer calls (an array of
+        gsim.routerstate.EVENT_DTYPE): each observer's events in array order,
+        observers independently; returns the uint8 answer of every event
+        (gsim_router_state_events).  A bad event fails the whole batch
+        (ValueError naming its index, nothing applied); a batch the space may
+        not hold is a GsimError (GSIM_ERANGE, nothing applied)."""
+        a = np.ascontiguousarray(events, dtype=np.dtype(_abi.ROUTER_EVENT_DTYPE))
+        res = np.zeros(len(a), dtype=np.uint8)
+        self._check(self.lib.gsim_router_state_events(self.h, _ptr(a) if len(a) else None, len(a),
+                                                      _ptr(res) if len(a) else None))
+        return res
+
+    def router_state_sweep(self, now: int):
+        """The time cache's sweep: drop the seen entries with expiry < now (gsim_router_state_sweep)."""
+        self._check(self.lib.gsim_router_state_sweep(self.h, int(now)))
+
+    def router_state_throttle(self, pairs) -> int:
+        """ThrottlePeer for (observer, peer) pairs: their promises are dropped;
+        returns how many (gsim_router_state_throttle)."""
+        p = np.ascontiguousarray(pairs, dtype=np.uint32).reshape(-1, 2)
+        dropped = ctypes.c_int64(0)
+        self._check(self.lib.gsim_router_state_throttle(self.h, _ptr(p) if len(p) else None, len(p),
+                                                        ctypes.byref(dropped)))
+        return dropped.value
+
+    def router_state_broken(self, now: int, apply_penalty: bool = False) -> np.ndarray:
+        """GetBrokenPromises of every observer: the promises with expire < now
+        are removed; one (observer, peer, count) row each, sorted, as a
+        structured array.  apply_penalty: each row is also AddPenalty(peer,
+        count) at the observer's peerScore (gsim_router_state_broken)."""
+        n = ctypes.c_int64(0)
+        cap = 256
+        while True:
+            out = np.zeros(cap, dtype=np.dtype(_abi.BROKEN_ROW_DTYPE))
+            rc = self.lib.gsim_router_state_broken(self.h, int(now), int(bool(apply_penalty)), _ptr(out), cap,
+                                                   ctypes.byref(n))
+            if rc == _abi.GSIM_ERANGE and n.value > cap:        # nothing was removed: once more with room
+                cap = n.value
+                continue
+            self._check(rc)
+            return out[:n.value]
+
+    def router_state_stats(self) -> dict:
+        """Live seen entries and promises, events applied, entries swept,
+        promises fulfilled or throttled, promises broken (gsim_router_state_stats)."""
+        out = np.zeros(6, dtype=np.int64)
+        self._check(self.lib.gsim_router_state_stats(self.h, _ptr(out)))
+        return dict(zip(["seen", "promises", "events", "swept", "fulfilled", "broken"], (int(x) for x in out)))
+
     def set_direct_peers(self, flags):
         """WithDirectPeers as per-edge flags (edge order; None clears)
         (gsim_set_direct_peers; gossipsub.go:352-374)."""

@@ -1127,6 +1127,104 @@ int gsim_score_tracer_stats(gsim_handle* h, int64_t* out4);
  * gsim_score_tracer_config; 1 while the engine holds such increments}. */
 int gsim_score_tracer_settled(gsim_handle* h, int64_t* out2);
 
+/* ---- router state: the seen cache and the IWANT promises from outside ------
+ * The two id-keyed structures a router consults around the score tracer, for
+ * the same callers (they own the routing; the engine keeps the state):
+ *   the seen cache (timecache/, pubsub.go:986-995, 1150-1162,
+ *   validation.go:307), which tells a ValidateMessage from a DuplicateMessage;
+ *   the gossip tracer's promises (gossip_tracer.go:48-200), whose broken ones
+ *   are the only source of P7 (gossipsub.go:1620-1625 -> AddPenalty).
+ * Both are kept per observer, as the CPU oracle restates them (orc_tcache_*,
+ * orc_gtracer_*).  The message cache is not here: it belongs with the
+ * payloads, which the caller holds.
+ *
+ * Ordering: as for the score tracer.  The events of one observer take effect
+ * in array order, observers are independent, the array need not be grouped,
+ * result[k] belongs to ev[k].
+ *
+ * The engine's own seen-set, promise ring and trace (gsim_round) are neither
+ * read nor written by these calls.  Single engines only: a shard of a group
+ * returns GSIM_ESTATE from every call. */
+#define GSIM_RS_SEEN_ADD 0   /* markSeen = TimeCache.Add: result 1 new, 0 already there */
+#define GSIM_RS_SEEN_HAS 1   /* seenMessage = TimeCache.Has: result 1 there, 0 not */
+#define GSIM_RS_PROMISE  2   /* gossipTracer.AddPromise(peer, ids) with the id already picked (the caller
+                                draws rand.Intn): result 1 a new (id, peer) promise expiring at
+                                now + followup, 0 it existed (its expiry is not renewed,
+                                gossip_tracer.go:65-74) */
+#define GSIM_RS_FULFILL  3   /* fulfillPromise(id) (gossip_tracer.go:119-141): every peer's promise of
+                                that id at the observer is dropped; result = how many, saturating at 255 */
+
+typedef struct gsim_router_event {   /* 32 bytes */
+    uint64_t mid;        /* message id */
+    int64_t  now_ns;     /* time.Now() as the router saw it */
+    uint32_t observer;   /* the router whose seen cache / gossip tracer receives the call */
+    uint32_t peer;       /* PROMISE: the peer that advertised the id; ignored otherwise */
+    uint8_t  kind;       /* GSIM_RS_* */
+    uint8_t  _pad[7];
+} gsim_router_event;
+
+typedef struct gsim_broken_row {     /* GetBrokenPromises: one (observer, peer) and its count */
+    uint32_t observer, peer, count, _pad;
+} gsim_broken_row;
+
+/* Size both structures: room for seen_cap seen entries and promises_cap
+ * promises alive at a time, over all observers.  strategy: 0 first-seen (the
+ * expiry is fixed at the first Add), 1 last-seen (every Add and every
+ * successful Has sets it to now + ttl).  seen_ttl_ns 0: TimeCacheDuration,
+ * 120 s; followup_ns 0: the engine's IWantFollowupTime.  Calling it again
+ * drops everything.  Needs a graph (GSIM_ESTATE); a new graph drops the
+ * configuration. */
+int gsim_router_state_config(gsim_handle* h, int64_t seen_cap, int64_t promises_cap, int32_t strategy,
+                             int64_t seen_ttl_ns, int64_t followup_ns);
+
+/* Apply n events; result[k] (may be NULL) receives ev[k]'s answer.  The whole
+ * batch is checked first: GSIM_EINVAL, with the first offending index in
+ * gsim_last_error and nothing applied, on an unknown kind, an observer >= N,
+ * a PROMISE whose peer is no connection (CSR neighbour) of the observer (the
+ * other kinds ignore peer), or a time that goes backwards for an observer,
+ * within the batch or against its last router event (this clock is separate
+ * from the score tracer's), or a time above INT64_MAX - max(seen_ttl_ns,
+ * followup_ns): an expiry is now + lifetime and must fit an int64 (any other
+ * time, negative ones included, is accepted).  GSIM_ERANGE, nothing applied, when the live seen
+ * entries plus the batch's SEEN_ADD events exceed seen_cap, or the live
+ * promises plus its PROMISE events exceed promises_cap.  Presence in the seen
+ * cache never depends on the clock: only gsim_router_state_sweep removes
+ * entries.  GSIM_ESTATE before gsim_router_state_config.  Synchronizes. */
+int gsim_router_state_events(gsim_handle* h, const gsim_router_event* ev, int64_t n, uint8_t* result);
+
+/* The time cache's background sweep (timecache/util.go:26-35): drop every seen
+ * entry with expiry < now_ns (strict: expiry == now_ns stays).  Their space
+ * is reusable afterwards, and an id added again is new.  Synchronizes. */
+int gsim_router_state_sweep(gsim_handle* h, int64_t now_ns);
+
+/* ThrottlePeer (gossip_tracer.go:182-200) for n (observer, peer) pairs
+ * (pairs[2q], pairs[2q + 1]): every promise of that peer at that observer is
+ * dropped; *dropped (may be NULL) their number.  GSIM_EINVAL, nothing dropped,
+ * with the first offending pair in gsim_last_error, on an observer >= N or a
+ * peer that is no connection of it.  Runs between batches (the reference
+ * calls it from the control path, asynchronously to message events).
+ * Synchronizes. */
+int gsim_router_state_throttle(gsim_handle* h, const uint32_t* pairs, int64_t n, int64_t* dropped);
+
+/* GetBrokenPromises (gossip_tracer.go:79-115) of every observer: the promises
+ * with expire < now_ns (strict) are removed and counted, one row per
+ * (observer, peer), sorted by (observer, peer).  *n is always set; when cap
+ * is too small: GSIM_ERANGE and nothing is removed.  apply_penalty != 0: each
+ * row also does what a GSIM_EV_ADD_PENALTY event of (observer, peer, count)
+ * does to GSIM_F_BP, the silent return for a peer without peerStats included.
+ * Space: the pool entries and table records of fulfilled, throttled and
+ * broken promises are free again at once as far as the capacity check of
+ * gsim_router_state_events goes (it counts live promises; a batch that needs
+ * the space compacts table and pool first), and physically after every
+ * throttle and broken call, which rebuild both.  Synchronizes. */
+int gsim_router_state_broken(gsim_handle* h, int64_t now_ns, int32_t apply_penalty, gsim_broken_row* out, int64_t cap,
+                             int64_t* n);
+
+/* out6 = {live seen entries, live promises, events applied, seen entries
+ * swept, promises fulfilled + throttled, promises broken} since
+ * gsim_router_state_config. */
+int gsim_router_state_stats(gsim_handle* h, int64_t* out6);
+
 /* Copy the score snapshot (E doubles, edge order) to host. */
 int gsim_read_scores(gsim_handle* h, double* out);
 
@@ -1226,6 +1324,12 @@ typedef enum gsim_kernel_class {
     GSIM_K_TRACER_SORT,        /* gsim_score_tracer_events: grouping the batch by observer */
     GSIM_K_TRACER_RESOLVE,     /* ... the events' edges and the batch checks */
     GSIM_K_TRACER_APPLY,       /* ... the per-observer walk over the events */
+    GSIM_K_ROUTER_SORT,        /* gsim_router_state_events: grouping the batch by observer */
+    GSIM_K_ROUTER_RESOLVE,     /* ... the PROMISE events' edges and the batch checks */
+    GSIM_K_ROUTER_APPLY,       /* ... the per-observer walk over the events */
+    GSIM_K_ROUTER_SWEEP,       /* gsim_router_state_sweep: the seen table's rebuild */
+    GSIM_K_ROUTER_BROKEN,      /* gsim_router_state_broken / _throttle: the promise kernels, sort and rebuild (device
+                                  work only); also the compaction a batch of gsim_router_state_events runs first */
     GSIM_K__COUNT
 } gsim_kernel_class;
 /* Enable (1) or disable (0) recording; clears recorded totals. */
